@@ -1,25 +1,32 @@
 """Headline benchmark: Mray/s of the per-pixel path-trace kernel (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5] [--variant -1] [--tiled-devices 0,0]
+                    [--dump-outputs DIR] [--full]
 
 A step is one frame of the hot path (Kernel.cu:102-158 → librt_hip.so rt_render) over the whole image;
 inputs (scene tables, RNG state) are resident in HBM before the timed region.  Rays are counted by the
 kernel itself (one closest-hit query = one iteration of color()'s loop, Kernel.cu:39).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, ms_per_step,
+kernel_ms, rays_per_frame).  `--dump-outputs DIR` then writes what the last timed step left in the caller's
+buffers as DIR/<name>.npy (dump_outputs).  Everything else is behind `--full`: the counting pass and the
+roofline block, the Philox and other-state-layout timings, the CPU baseline, the synchronous gather timing at
+N > 1 and other_configs (the other BASELINE configs named below).
 
   --config c2 (default, the BASELINE metric): N = 1 renders config 2 (1920×1080, 64 spp, depth 8, RTIOW
       final scene).  N > 1 (one process per GPU) is weak scaling: the image grows to round(1920·√N) ×
       round(1080·√N) (same camera and field of view, ≈2.07 M pixels per GPU), split in block-cyclic 16-row
       bands; every frame is gathered to rank 0 over RCCL on the collective's own stream while the next frame
       renders (parallel.BandGather; the last frame's gather is inside the timed region, gather_ms is the part
-      of it the render stream waited for).  The line carries other_configs: BASELINE config 4 (the 7680×4320,
-      128 spp frame split over the N ranks + RCCL gather) at every N, and configs 5 and 3 at N = 1.
+      of it the render stream waited for).  With --full the line carries other_configs: BASELINE config 4 (the
+      7680×4320, 128 spp frame split over the N ranks + RCCL gather) at every N, and configs 5 and 3 at N = 1.
   --config c3: BASELINE config 3 (3840×2160, 256 spp, depth 16, Cornell box), one GPU.
   --config c4: BASELINE config 4 as configured, strong scaling: one 7680×4320, 128 spp, depth 8 RTIOW frame
       split over the N ranks in 16-row bands (N = 1 renders all of it) + the RCCL gather, whose time is
       reported apart (gather_ms).
   --config c5: BASELINE config 5 (1920×1080, 1 spp, depth 4, three 8192×4096 image textures), one GPU: a step
       is one progressive frame of the scripted moving camera (new InputStruct, accumulation reset because the
-      camera moved, one RT_FLAG_ACCUMULATE frame).  Roofline against HBM.
+      camera moved, one RT_FLAG_ACCUMULATE frame).  Roofline (--full) against HBM.
   --tiled-devices d0,d1,…: single process, rt_tiled_* C ABI (one band rank per listed device, peer-copy
       gather): the path a C++ viewer uses without torch.distributed.
 
@@ -56,6 +63,7 @@ PEAK_HBM_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E ≈ 8 TB/s per GPU
 FLOP_BOX, FLOP_SPHERE, FLOP_RECT, FLOP_RAY, FLOP_PRIMARY = 21, 23, 12, 60, 40
 F_REF_PER_RAY = 21 * 50.7 + 23 * 6.9 + 60  # reference BVH on C2: ≈1.28 kFLOP/ray
 C5_FRAMES = 60  # C5's scripted orbit (scenes.moving_camera)
+DUMP_BUDGET_BYTES = 60 * 10**6  # --dump-outputs: all files together stay under 64 MB
 
 METRICS = {
     "c2": "Mray/s (and ms/frame) at 1920x1080, 64 spp, depth 8, random-spheres",
@@ -86,16 +94,22 @@ def parse_args(argv=None):
     ap.add_argument("--state-layout", choices=("soa", "curand"), default="soa",
                     help="XORWOW states: soa = native six uint32 planes (RT_FLAG_STATE_SOA, 24 B/pixel, the same "
                          "streams); curand = the reference's 48-B curandState structs (the LaunchKernel layout)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (counting pass), Philox and "
+                         "other-layout timings, CPU baseline, synchronous gather, other_configs")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-philox-line", action="store_true", help="skip the secondary Philox-mode timing (N=1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-philox-line", action="store_true",
+                    help="--full: skip the secondary Philox-mode timing (N=1)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank renders on device 0 (use with --backend gloo)")
     ap.add_argument("--tiled-devices", default="",
                     help="single-process multi-device split through the rt_tiled C ABI, e.g. 0,1,2,3 (or 0,0 on one GPU)")
     ap.add_argument("--no-config-lines", action="store_true",
-                    help="N=1 --config c2: skip the BASELINE config 3 and 5 figures attached to the headline line")
+                    help="--full --config c2: skip the other BASELINE configs' figures attached to the headline line")
     ap.add_argument("--tune", default="",
                     help="rt_set_tuning overrides as key=value[,key=value] (rt_tuning_key in include/rt_hip.h)")
     ap.add_argument("--dry-run", action="store_true",
@@ -126,8 +140,8 @@ def self_launch(args) -> int:
 
 def dry_run(args) -> None:
     """The launch path without a GPU: every rank joins a gloo group and gathers a synthetic band buffer of the
-    configured frame (its global row indices), and rank 0 checks the reassembled frame; for config 2 the same for
-    config 4's frame (the block other_configs.c4 of a GPU run)."""
+    configured frame (its global row indices), and rank 0 checks the reassembled frame; with --full, for config 2
+    the same for config 4's frame (the block other_configs.c4 of a --full GPU run)."""
     from cudaraytracer_amd.renderer import band_rows_of
     from cudaraytracer_amd import scenes
 
@@ -149,7 +163,7 @@ def dry_run(args) -> None:
 
     ok = gather_ok(args.config)
     oc = {"c4": {"frame_ok": gather_ok("c4"), "height": scenes.CONFIGS["c4"].height, "scaling": "strong",
-                 "band_rows": parallel.DEFAULT_BAND_ROWS}} if args.config == "c2" and not args.no_config_lines else None
+                 "band_rows": parallel.DEFAULT_BAND_ROWS}} if wants_other_configs(args) else None
     if rank == 0:
         line = {"dry_run": True, "world_size": world, "gpus": args.gpus, "config": args.config,
                 "band_rows": parallel.DEFAULT_BAND_ROWS, "frame_ok": ok}
@@ -247,6 +261,34 @@ def pmc_profile(config: str, rng: str, state_layout: str = "curand") -> dict:
     return {k: d[k] for k in keys if k in d}
 
 
+def rgba8_planes(pos: torch.Tensor, height: int, width: int):
+    """A device RGBA8 framebuffer (one int32 per pixel) as a host (H, W, 4) float32 array of its R, G, B, A bytes."""
+    import numpy as np
+
+    return pos.cpu().numpy().view(np.uint8).reshape(height, width, 4).astype(np.float32)
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array of `arrays` (per pixel: (H, W, C)) as path/<name>.npy in float32.  The files
+    share DUMP_BUDGET_BYTES equally; an array over its share is cut to a fixed sample of its pixels (the sorted
+    choice of numpy's default_rng(0), the same pixels in every run of the same shape) and saved as (pixels, C)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        keep = share // (a.shape[-1] * 4)
+        px = a.reshape(-1, a.shape[-1])
+        if px.shape[0] > keep:
+            a = px[np.sort(np.random.default_rng(0).choice(px.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def wants_other_configs(args) -> bool:
+    return args.full and args.config == "c2" and not args.no_config_lines
+
+
 def run_tiled(args, cfg) -> None:
     """--tiled-devices: one process, rt_tiled_* (band rank r on devices[r], peer-copy gather into one frame)."""
     from cudaraytracer_amd import scenes
@@ -278,6 +320,8 @@ def run_tiled(args, cfg) -> None:
                    "parallelism": f"{len(devices)} band ranks (rt_tiled), 16-row bands, peer-copy gather"},
         "render_ms": round(sum(render_ms) / len(render_ms), 3), "gather_ms": round(sum(gather_ms) / len(gather_ms), 3),
     }), flush=True)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": rgba8_planes(t.pos, cfg.height, cfg.width)})
     t.close()
 
 
@@ -335,13 +379,15 @@ def run_rank(args) -> dict | None:
     r.render_init()
     frame_flags = abi.RT_FLAG_ACCUMULATE if progressive else 0
 
-    # Counting pass (untimed, RNG state not advanced): executed box / primitive tests for F_exec.
-    r.counters.zero_()
-    r.render(scene, cfg.spp, cfg.depth, inputs,
-             flags=frame_flags | abi.RT_FLAG_COUNT_TESTS | abi.RT_FLAG_NO_STATE_WRITEBACK)
-    torch.cuda.synchronize()
-    c = [int(x) for x in r.counters.tolist()]
-    f_launch = flop_model(c)
+    # --full: counting pass (untimed, RNG state not advanced): executed box / primitive tests for F_exec.
+    c, f_launch = None, 0
+    if args.full:
+        r.counters.zero_()
+        r.render(scene, cfg.spp, cfg.depth, inputs,
+                 flags=frame_flags | abi.RT_FLAG_COUNT_TESTS | abi.RT_FLAG_NO_STATE_WRITEBACK)
+        torch.cuda.synchronize()
+        c = [int(x) for x in r.counters.tolist()]
+        f_launch = flop_model(c)
 
     frame_no = [0]
 
@@ -396,12 +442,18 @@ def run_rank(args) -> dict | None:
             ev[i][2].record(stream)
     if not per_step:
         ev[0][1].record(stream)
-    if world > 1:
-        gatherer.finish()  # the last frame's gather is inside the timed region
+    frame = gatherer.finish() if world > 1 else None  # the last frame's gather is inside the timed region
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left with the caller: the RGBA8 frame (N > 1: the frame gathered on rank 0)
+        # and, for the progressive config, the float4 accumulator behind it
+        out = {"image": rgba8_planes(r.pos if frame is None else frame, cfg.height, cfg.width)}
+        if progressive:
+            out["accum"] = r.accum.cpu().numpy().reshape(cfg.height, cfg.width, 4)
+        dump_outputs(args.dump_outputs, out)
     if per_step:
         kernel_ms = sum(a.elapsed_time(b) for a, b, _ in ev) / args.steps
         gather_ms = sum(b.elapsed_time(g) for _, b, g in ev) / args.steps
@@ -416,7 +468,7 @@ def run_rank(args) -> dict | None:
     elapsed, kernel_ms, gather_ms = float(stats[0]), float(stats[1]), float(stats[2])
     rays_all = int(tot[0])
     gather = None
-    if world > 1:  # one more gather of the last frame, alone and synchronous: the transfer's own time
+    if world > 1 and args.full:  # one more gather of the last frame, alone and synchronous: the transfer's own time
         counts = parallel.local_row_counts(cfg.height, band, world)
         nbytes = (world - 1) * max(counts) * cfg.width * 4  # rank 0 receives every other rank's padded band buffer
         times = []
@@ -465,6 +517,8 @@ def run_rank(args) -> dict | None:
         }
         if gather is not None:
             line["gather"] = gather
+        if not args.full:
+            return line
         if progressive:
             line["roofline"] = hbm_roofline(args, cfg, r, c, kernel_ms)
         else:
@@ -576,6 +630,7 @@ def other_configs(args, world: int) -> dict | None:
         sub = argparse.Namespace(**vars(args))
         sub.config, sub.steps, sub.warmup = name, steps, warmup
         sub.no_cpu_baseline = sub.no_philox_line = True
+        sub.dump_outputs = None
         o = run_rank(sub)
         if o is not None:
             out[name] = {k: o[k] for k in ("metric", "value", "unit", "ms_per_step", "kernel_ms", "gather_ms",
@@ -601,7 +656,7 @@ def main() -> None:
         return
     line = run_rank(args)
     world = parallel.env_rank()[1]
-    if args.config == "c2" and not args.no_config_lines:
+    if wants_other_configs(args):
         oc = other_configs(args, world)
         if line is not None:
             line["other_configs"] = oc

@@ -32,14 +32,49 @@ def test_self_launch_spawns_n_ranks(gpus, config):
 
 @pytest.mark.parametrize("gpus", [2, 3, 8])
 def test_default_line_carries_config4_block(gpus):
-    """the driver's default `bench.py --gpus N` (config 2) also measures BASELINE config 4 (the
+    """the driver's `bench.py --gpus N --full` (config 2) also measures BASELINE config 4 (the
     7680x4320 frame split over the N ranks + the gather): the rehearsed launch carries other_configs.c4."""
-    p = _bench("--gpus", str(gpus), "--dry-run")
+    p = _bench("--gpus", str(gpus), "--dry-run", "--full")
     assert p.returncode == 0, p.stderr[-2000:]
     line = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")][0]
     c4 = line["other_configs"]["c4"]
     assert c4["frame_ok"] is True and c4["height"] == 4320 and c4["scaling"] == "strong"
     assert line["world_size"] == gpus and line["frame_ok"] is True
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full the launch rehearses the configured frame alone: no other_configs block."""
+    p = _bench("--gpus", "1", "--dry-run")
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = [json.loads(ln) for ln in p.stdout.splitlines() if ln.startswith("{")][0]
+    assert "other_configs" not in line and line["frame_ok"] is True and line["world_size"] == 1
+
+
+def test_dump_outputs_writes_bounded_float32(tmp_path):
+    """--dump-outputs: float32 .npy files within the byte budget; an array over its share is cut to the same
+    fixed sample of pixels on every call."""
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    assert bench.parse_args([]).dump_outputs is None and bench.parse_args([]).full is False
+    assert bench.parse_args(["--dump-outputs", "d", "--full"]).dump_outputs == "d"
+    small = np.arange(5 * 7 * 4, dtype=np.uint8).reshape(5, 7, 4)
+    big = np.arange(1000 * 4, dtype=np.float64).reshape(25, 40, 4)
+    budget = bench.DUMP_BUDGET_BYTES
+    bench.DUMP_BUDGET_BYTES = 2 * 300 * 16  # 300 pixels of 4 floats per file
+    try:
+        for d in ("a", "b"):
+            bench.dump_outputs(str(tmp_path / d), {"image": small, "accum": big})
+    finally:
+        bench.DUMP_BUDGET_BYTES = budget
+    img, acc = np.load(tmp_path / "a" / "image.npy"), np.load(tmp_path / "a" / "accum.npy")
+    assert img.dtype == np.float32 and np.array_equal(img, small)
+    assert acc.dtype == np.float32 and acc.shape == (300, 4)
+    rows = (acc[:, 0] / 4).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(acc, big.reshape(-1, 4)[rows])
+    assert np.array_equal(acc, np.load(tmp_path / "b" / "accum.npy"))
 
 
 def test_fewer_gpus_than_requested_fails_loudly():

@@ -3,6 +3,7 @@ validation, the BVH build and the reference-graph flattener (no device needed)."
 from __future__ import annotations
 
 import ctypes as C
+import json
 import os
 
 import numpy as np
@@ -249,7 +250,7 @@ QUEUE_GUIDE_DEFAULT = 0
 # ---------------------------------------------------------------------------------------------------
 # Image loading (LoadImage, Utils/RawStbImage.h:11-22) and the reference's own texture assets
 # ---------------------------------------------------------------------------------------------------
-REF_TEXTURES = "/root/reference/assets/textures"
+REF_TEXTURES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_textures.json")
 
 
 def test_load_image_mirrors_loadimage(tmp_path):
@@ -277,13 +278,23 @@ def test_textured_scene_takes_caller_images():
         scenes.builtin(scenes.SCENE_TEXTURED, images=[imgs[0], imgs[1], imgs[2][:, :, :1]])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_TEXTURES), reason="the reference's assets are not here")
-def test_reference_texture_files_load_as_rgb8():
-    """The reference's own planet maps, read in place (nothing derived from them is stored): each decodes to the
-    RGB8 layout Image::value reads (Texture.cuh:76) and sits on the textured scene's spheres."""
-    imgs = [scenes.load_image(os.path.join(REF_TEXTURES, n)) for n in ("8k_earth_nightmap.jpg", "8k_stars.jpg",
-                                                                        "8k_sun.jpg")]
+def test_reference_texture_files_load_as_rgb8(tmp_path):
+    """JPEG files with the names and sizes of the reference's own planet maps (recorded in
+    tests/golden/reference_textures.json; the texels are procedural, nothing derived from the assets is stored):
+    each decodes to the RGB8 layout Image::value reads (Texture.cuh:76) and sits on the textured scene's spheres."""
+    from PIL import Image
+
+    with open(REF_TEXTURES) as f:
+        files = json.load(f)["files"]
+    assert [f["name"] for f in files] == ["8k_earth_nightmap.jpg", "8k_stars.jpg", "8k_sun.jpg"]
+    for f in files:
+        h, w, c = f["shape"]
+        y, x = np.mgrid[0:h, 0:w].astype(np.uint16)
+        texels = np.stack([(x >> 5) ^ (y >> 4), x >> 6, y >> 4][:c], axis=-1).astype(np.uint8)
+        Image.fromarray(texels).save(tmp_path / f["name"], quality=50)
+    imgs = [scenes.load_image(str(tmp_path / f["name"])) for f in files]
     assert [im.shape for im in imgs] == [(4096, 8192, 3), (4096, 8192, 3), (2048, 4096, 3)]
+    assert all(im.dtype == np.uint8 and im.flags.c_contiguous for im in imgs)
     sc = scenes.builtin(scenes.SCENE_TEXTURED, images=imgs)
     d = sc.desc()
     assert d.num_images == 3 and (d.images[2].width, d.images[2].height) == (4096, 2048)

@@ -9,6 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 STEPS=${STEPS:-tests smoke bench prof benchcfg}
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # a session's bench lines carry everything (roofline, CPU baseline, other configs)
 for step in $STEPS; do
   case $step in
     tests)
@@ -38,7 +39,7 @@ for step in $STEPS; do
     rehearse)  # bench.py's self-launched N > 1 path with every rank on device 0 (gloo gather): C2 weak, C4 strong
       for n in ${REHEARSE_N:-2 4}; do
         for cfg in c2 c4; do
-          timeout -k 10 400 python bench.py --gpus $n --steps 3 --warmup 1 --config $cfg --backend gloo \
+          timeout -k 10 400 python bench.py --full --gpus $n --steps 3 --warmup 1 --config $cfg --backend gloo \
             --share-gpu --no-cpu-baseline --no-philox-line > gpurun_out/rehearse_${cfg}_n$n.log 2>&1 || exit $?
           tail -1 gpurun_out/rehearse_${cfg}_n$n.log
         done

@@ -46,6 +46,9 @@ EXPORTED = [
     "rt_set_pixel_cost",
     "rt_set_ray_dump",
     "rt_trace_rays",
+    "rt_gbuffer",
+    "rt_denoise",
+    "rt_denoise_scratch_bytes",
     "rt_last_kernel_ms",
     "rt_last_variant",
     "rt_last_launch_host_ms",
@@ -98,6 +101,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_set_pixel_cost.argtypes = [C.c_void_p, C.c_uint64]
     lib.rt_set_ray_dump.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]
     lib.rt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    lib.rt_gbuffer.argtypes = [vp, P(abi.GBufferArgs), vp]
+    lib.rt_denoise.argtypes = [P(abi.DenoiseArgs), vp]
+    lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.rt_denoise_scratch_bytes.restype = C.c_uint64
     lib.rt_last_kernel_ms.restype = C.c_float
     lib.rt_last_variant.restype = C.c_int
     lib.rt_last_launch_host_ms.restype = C.c_float

@@ -22,6 +22,8 @@ RT_FLAG_COUNT_TESTS = 1 << 4
 RT_FLAG_RNG_PHILOX = 1 << 5
 RT_FLAG_STATE_SOA = 1 << 6
 RT_FLAG_ACCUMULATE_RESET = 1 << 7
+RT_DENOISE_DEMODULATE = 1 << 0
+RT_DENOISE_COLOR_IS_SUM = 1 << 1
 COUNTERS_WORDS = 24  # RT_COUNTERS_WORDS: the counters buffer with RT_FLAG_COUNT_TESTS
 PHILOX_MAX_SPP = 16384  # RT_PHILOX_MAX_SPP
 # rt_set_tuning keys (rt_tuning_key in include/rt_hip.h)
@@ -157,6 +159,40 @@ class RenderArgs(C.Structure):
         ("rng_seed", C.c_uint64),
         ("rng_frame", C.c_uint32),
         ("reserved2", C.c_uint32),
+    ]
+
+
+class GBufferArgs(C.Structure):
+    _fields_ = [
+        ("normal_depth", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("prim_id", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+        ("tiling", Tiling),
+        ("inputs", InputStruct),
+    ]
+
+
+class DenoiseArgs(C.Structure):
+    _fields_ = [
+        ("color", C.c_void_p),
+        ("normal_depth", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("prim_id", C.c_void_p),
+        ("out_color", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("scratch", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("iterations", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("sigma_c", C.c_float),
+        ("sigma_n", C.c_float),
+        ("sigma_z", C.c_float),
+        ("reserved", C.c_uint32),
+        ("tiling", Tiling),
     ]
 
 

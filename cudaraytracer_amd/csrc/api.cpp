@@ -70,6 +70,9 @@ static void free_device(DeviceScene* s) {
     if (s->bvh_boxes) (void)hipFree((void*)s->bvh_boxes);
     if (s->bvh_ref_pairs) (void)hipFree((void*)s->bvh_ref_pairs);
     s->bvh_ref_nodes = s->bvh_boxes = s->bvh_ref_pairs = nullptr;
+    if (s->prim_source) (void)hipFree((void*)s->prim_source);
+    if (s->flat_source) (void)hipFree((void*)s->flat_source);
+    s->prim_source = s->flat_source = nullptr;
     if (s->mats) (void)hipFree((void*)s->mats);
     if (s->imgs) (void)hipFree((void*)s->imgs);  // texels: owned by rt_scene::texel_block
     s->nodes = s->prims = s->mats = nullptr;
@@ -109,6 +112,10 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     d.bvh_ref_pairs = p;
     d.flat_runs[0] = h.flat_runs[0];
     d.flat_runs[1] = h.flat_runs[1];
+    if ((rc = upload(h.prim_source, &p, "hipMalloc/hipMemcpy(prim_source)"))) goto fail;
+    d.prim_source = p;
+    if ((rc = upload(h.flat_source, &p, "hipMalloc/hipMemcpy(flat_source)"))) goto fail;
+    d.flat_source = p;
     if ((rc = upload(h.mats, &p, "hipMalloc/hipMemcpy(materials)"))) goto fail;
     d.mats = p;
     if ((rc = upload(h.imgs, &p, "hipMalloc/hipMemcpy(images)"))) goto fail;
@@ -129,7 +136,8 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     d.has_textures = h.has_textures;
     d.has_rects = h.has_rects;
     d.device_bytes = (h.nodes.size() + h.nodes48.size() + h.refs.size() + h.prims.size() + h.prims_flat.size() + h.ref_nodes.size() +
-                      h.flat_boxes.size() + h.flat_ref_pairs.size() + h.bvh_ref_nodes.size() + h.bvh_boxes.size() + h.bvh_ref_pairs.size() + h.mats.size()) * 4 +
+                      h.flat_boxes.size() + h.flat_ref_pairs.size() + h.bvh_ref_nodes.size() + h.bvh_boxes.size() + h.bvh_ref_pairs.size() + h.mats.size() +
+                      h.prim_source.size() + h.flat_source.size()) * 4 +
                      h.imgs.size() * 4 + h.texels.size();
     *out = s;
     return RT_OK;

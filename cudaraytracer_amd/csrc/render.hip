@@ -35,6 +35,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "rt_epilogue.h"
 #include "rt_internal.h"
 #include "rt_scene_device.h"
 
@@ -130,7 +131,6 @@ __device__ __forceinline__ float recip_in_range(const float s) {
     return in_rcp_range(s) ? rcp_rn(s) : 0.0f;
 }
 __device__ __forceinline__ f3 reflect(f3 v, f3 n) { return sub(v, scale(2.0f * dot(v, n), n)); }
-__device__ __forceinline__ float clampf(float x, float a, float b) { return (x < a) ? a : ((x > b) ? b : x); }
 __device__ __forceinline__ f3 xyz(float4 v) { return mk(v.x, v.y, v.z); }
 
 // ---------------------------------------------------------------------------------------------------
@@ -830,15 +830,7 @@ __device__ __forceinline__ f3 texture_value(const float4& m0, const float4& m1, 
     return f.pending ? texture_resolve(f, *reinterpret_cast<const UnalignedU32*>(f.texel)) : f.color;
 }
 
-__device__ __forceinline__ uint32_t f2u8(float f) { return f != f ? 0u : (uint32_t)(int)f; }
-
-// RgbToInt (Kernel.cu:12-19)
-__device__ __forceinline__ uint32_t rgb_to_int(float r, float g, float b) {
-    r = clampf(r, 0.0f, 255.0f);
-    g = clampf(g, 0.0f, 255.0f);
-    b = clampf(b, 0.0f, 255.0f);
-    return (255u << 24) | (f2u8(b) << 16) | (f2u8(g) << 8) | f2u8(r);
-}
+// (f2u8, rgb_to_int: rt_epilogue.h, shared with denoise.hip)
 
 __device__ __forceinline__ uint32_t global_row(const KParams& P, uint32_t local_row) {
     const uint32_t band = local_row / P.band_rows, within = local_row - band * P.band_rows;
@@ -3436,6 +3428,138 @@ __device__ __forceinline__ void curand_init_state(unsigned long long seed, uint3
     *reinterpret_cast<uint4*>(st + 8) = make_uint4(0u, 0u, 0u, 0u);  // boxmuller_extra, pad, extra_double
 }
 
+// ---------------------------------------------------------------------------------------------------
+// First-hit G-buffer (rt_gbuffer): one wave per 8×8 pixel tile as v3, one camera ray per pixel through the pixel
+// centre, no RNG, no regeneration or persistence.  BVH scenes: v3's traversal on 16-bit LDS stacks run to completion
+// (threshold 0), as trace_rays_kernel; small scenes (those rt_render gives to the flat kernels): flat_trace over the
+// flat table.  Both return the geometric closest hit (rt_trace_rays' semantics: no reference replay).  The hit record
+// and the texture value follow shade().  The kernel's own arguments follow a KParams (the camera, tiling and scene
+// fields the shared device functions read).
+// ---------------------------------------------------------------------------------------------------
+struct GBufParams {
+    KParams K;
+    float4* normal_depth;
+    float4* albedo;
+    int32_t* prim_id;
+    const int32_t* source;  // per record of K.prims the hittable's index in the caller's description
+};
+
+// camera_ray (Kernel.cu:139-146) with the two jitter numbers given: the same operations in the same order
+template <class PP>
+__device__ __forceinline__ void camera_ray_at(PP P, const Camera& cam, const float xi1, const float xi2, f3& ro, f3& rd) {
+    const float u = div_rn(cam.xf + xi1, P->width_f, P->inv_width);
+    const float v = div_rn(cam.yf + xi2, P->width_f, P->inv_width);
+    const f3 dist = add(scale(u, cam.right), scale(v, cam.up));
+    const f3 start = add(add(scale(P->near_plane, dist), cam.origin), cam.fov_fwd);
+    const f3 second = add(add(scale(P->far_plane, dist), cam.k10_fwd), cam.origin);
+    ro = start;
+    rd = normalize(sub(second, start));
+}
+
+// The pixel's three records from its closest hit (hit: index into K.prims or -1; tag: type | material << 4).
+__device__ __forceinline__ void gbuffer_store(const GBufParams& G, const size_t pix, const int hit, const uint32_t tag,
+                                              const float t, const f3 ro, const f3 rd) {
+    const KParams* P = &G.K;
+    if (hit < 0) {  // sky (Kernel.cu:41-44), as shade()
+        const float len = length(rd);
+        float q;
+        if (in_rcp_range(len)) q = div_rn(rd.y, len, rcp_rn(len));
+        else q = rd.y / len;
+        const float tt = 0.5f * (q + 1.0f);
+        const f3 c = add(scale(1.0f - tt, mk(P->bg0[0], P->bg0[1], P->bg0[2])), scale(tt, mk(P->bg1[0], P->bg1[1], P->bg1[2])));
+        if (G.normal_depth) G.normal_depth[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        if (G.albedo) G.albedo[pix] = make_float4(c.x, c.y, c.z, 1.0f);
+        if (G.prim_id) G.prim_id[pix] = -1;
+        return;
+    }
+    const float4 p0 = P->prims[2 * hit + 0], p1 = P->prims[2 * hit + 1];
+    const uint32_t type = tag & 15u, mat = tag >> 4;
+    const float4 m0 = P->mats[3 * mat + 0];
+    const uint32_t mtype = __float_as_uint(m0.x) & 15u, ttype = (__float_as_uint(m0.x) >> 4) & 15u;
+    f3 p, normal;
+    float hu = 0.0f, hv = 0.0f;
+    if (type == RT_SPHERE) {  // hit record of Sphere::Hit (Hittable.cuh:91-95)
+        p = add(ro, scale(t, rd));
+        normal = divs_rn(sub(p, xyz(p0)), p0.w, p1.y);
+        if (ttype == RT_IMAGE && mtype != RT_DIELECTRIC) {  // GetSphereUV (Hittable.cuh:119-125)
+            const float theta = rt_acosf(-normal.y);
+            const float phi = rt_atan2f(-normal.z, normal.x) + 3.141592654f;
+            hu = fdiv(phi, 2 * 3.141592654f);
+            hv = fdiv(theta, 3.141592654f);
+        }
+    } else {  // hit record of *Rect::Hit (Hittable.cuh:155-166)
+        const float oa = type == RT_YZRECT ? ro.y : ro.x, da = type == RT_YZRECT ? rd.y : rd.x;
+        const float ob = type == RT_XYRECT ? ro.y : ro.z, db = type == RT_XYRECT ? rd.y : rd.z;
+        const float xx = oa + t * da;
+        const float yy = ob + t * db;
+        hu = fdiv(xx - p0.y, p0.z - p0.y);
+        hv = fdiv(yy - p0.w, p1.x - p0.w);
+        const f3 outward = type == RT_XYRECT ? mk(0.0f, 0.0f, 1.0f)
+                           : type == RT_XZRECT ? mk(0.0f, 1.0f, 0.0f)
+                                               : mk(1.0f, 0.0f, 0.0f);
+        const bool front = dot(rd, outward) < 0;  // SetFaceNormal (Hittable.cuh:23-27)
+        normal = front ? outward : neg(outward);
+        p = add(ro, scale(t, rd));
+    }
+    f3 alb = mk(1.0f, 1.0f, 1.0f);  // Dielectric::Scatter's attenuation (Material.cuh:112)
+    if (mtype != RT_DIELECTRIC) {
+        const float4 m1 = P->mats[3 * mat + 1];
+        alb = xyz(m1);
+        if (ttype != RT_CONSTANT) {
+            const float4 m2 = P->mats[3 * mat + 2];
+            alb = texture_value(m0, m1, m2, ttype, hu, hv, p, P->imgs, P->texels);
+        }
+        if (mtype == RT_DIFFUSELIGHT) alb = scale(m0.z, alb);  // DiffuseLight::Emitted (Material.cuh:164-176)
+    }
+    if (G.normal_depth) G.normal_depth[pix] = make_float4(normal.x, normal.y, normal.z, t);
+    if (G.albedo) G.albedo[pix] = make_float4(alb.x, alb.y, alb.z, 1.0f);
+    if (G.prim_id) G.prim_id[pix] = G.source[hit];
+}
+
+template <bool FLAT>
+__global__ __launch_bounds__(64, 4) void gbuffer_kernel(const GBufParams G) {
+    const KParams* P = &G.K;
+    // every lane traces a ray (a partial tile's outside lanes trace their off-image pixel's and store nothing), so
+    // the wave-level steps of the traversal see 64 active lanes
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t bx = blockIdx.x % P->tiles_x, by = blockIdx.x / P->tiles_x;
+    const uint32_t x = bx * 8u + (lane & 7u), ly = by * 8u + (lane >> 3);
+    const bool inside = x < P->width && ly < P->local_rows;
+    const uint32_t g = global_row(*P, ly);
+    const size_t pix = (size_t)ly * P->width + x;
+    f3 ro, rd;
+    camera_ray_at(P, lane_camera(P, x, g), 0.5f, 0.5f, ro, rd);
+    int hit = -1;
+    uint32_t tag = 0u;
+    float t = FLT_MAX;
+    Counts cnt{0, 0, 0, 0, 0, 0, 0};
+    if constexpr (FLAT) {
+        bool replay;
+        flat_trace<false>(P->prims, P->ref_nodes, P->flat_boxes, P->num_prims, P->flat_runs[0], P->flat_runs[1], ro, rd, hit,
+                          tag, t, cnt, replay);
+    } else {
+        using Entry = uint16_t;
+        extern __shared__ float4 lds[];
+        Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
+        const __amdgpu_buffer_rsrc_t nrsrc =
+            __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+        stk[0] = (Entry)RefW<false>::kSentinel;
+        stk[64] = (Entry)RefW<false>::kSentinel;
+        Cursor c{(int)RefW<false>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+        uint32_t nrays = 0u;
+        v3_start_trace<false>(P->num_nodes, c, nrays);
+        while (__ballot(c.mode == MODE_TRAV) != 0) {
+            if (c.mode == MODE_TRAV)
+                v3_traverse<false, NODES_48, 0u, false, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, 0u, ro, rd, c, cnt, 64u,
+                                                               P->leaf_break);
+        }
+        hit = c.hit;
+        tag = c.tag;
+        t = c.t_best;
+    }
+    if (inside) gbuffer_store(G, pix, hit, tag, t, ro, rd);
+}
+
 __global__ __launch_bounds__(kBlock) void render_init_kernel(uint32_t* state, uint32_t width, uint32_t local_rows,
                                                               uint32_t band_rows, uint32_t num_ranks, uint32_t rank,
                                                               unsigned long long seed_base, uint32_t soa) {  // soa: plane size
@@ -3860,6 +3984,43 @@ int rt_set_ray_dump(void* rays, uint32_t capacity, uint32_t* count, uint32_t dep
     return RT_OK;
 }
 
+// Launch-uniform camera terms, with the binary32 operations of Kernel.cu:130-143 (rt_render, rt_gbuffer).
+static void fill_camera(dev::KParams& P, const rt_input_struct& in, const uint32_t width, const uint32_t height) {
+    P.width_f = (float)width;
+    P.inv_width = 1.0f / P.width_f;
+    P.cx = (float)width / 2.0f;
+    P.cy = (float)height / 2.0f;
+    P.near_plane = in.near_plane;
+    P.far_plane = in.far_plane;
+    {
+        volatile float up[3] = {in.up[0], in.up[1], in.up[2]};
+        volatile float fw[3] = {in.orientation[0], in.orientation[1], in.orientation[2]};
+        // rightV = Normalize(Cross(upV, forwardV)) (Kernel.cu:133, Math.cuh:157-161, 225-229)
+        volatile float cx = up[1] * fw[2] - up[2] * fw[1];
+        volatile float t = up[0] * fw[2] - up[2] * fw[0];
+        volatile float cy = -t;
+        volatile float cz = up[0] * fw[1] - up[1] * fw[0];
+        volatile float d0 = cx * cx, d1 = cy * cy, d2 = cz * cz;
+        volatile float dd = d0 + d1;
+        dd = dd + d2;
+        volatile float s = std::sqrt((float)dd);
+        volatile float inv = 1.0f / s;
+        P.right[0] = inv * cx;
+        P.right[1] = inv * cy;
+        P.right[2] = inv * cz;
+        volatile float k10 = 1.0f / in.fov;
+        k10 = k10 * 10.0f;
+        for (int i = 0; i < 3; i++) {
+            P.origin[i] = in.origin[i];
+            P.up[i] = in.up[i];
+            P.fov_fwd[i] = in.fov * fw[i];
+            P.k10_fwd[i] = k10 * fw[i];
+            P.bg0[i] = in.background_start[i];
+            P.bg1[i] = in.background_end[i];
+        }
+    }
+}
+
 int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t* hits, uint64_t* counters,
                   int count_tests, rt_stream stream) {
     if (!scene || (n && (!rays || !hits))) { set_error("rt_trace_rays: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
@@ -3892,6 +4053,75 @@ int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t*
         hipLaunchKernelGGL(dev::trace_rays_kernel<false>, dim3(grid), dim3(64), lds, s, P, (const float4*)rays, n, per_wave,
                            (int2*)hits);
     return hip_check(hipGetLastError(), "rt_trace_rays: kernel launch", RT_ERR_LAUNCH);
+}
+
+int rt_gbuffer(const rt_scene* scene, const rt_gbuffer_args* a, rt_stream stream) {
+    // (the arguments first: every check but the scene's own runs without a device)
+    if (!a) { set_error("rt_gbuffer: NULL args"); return RT_ERR_INVALID_ARGUMENT; }
+    if (a->reserved[0] != 0 || a->reserved[1] != 0) { set_error("rt_gbuffer: reserved fields must be 0"); return RT_ERR_INVALID_ARGUMENT; }
+    if (!a->normal_depth && !a->albedo && !a->prim_id) { set_error("rt_gbuffer: no output buffer"); return RT_ERR_INVALID_ARGUMENT; }
+    if (!scene) { set_error("rt_gbuffer: NULL scene"); return RT_ERR_INVALID_ARGUMENT; }
+    const rt_tiling& T = a->tiling;
+    if (a->width == 0 || a->height == 0 || T.local_rows == 0) return RT_OK;  // nothing to trace
+    if (T.band_rows == 0 || T.num_ranks == 0 || T.rank >= T.num_ranks) {
+        set_error("rt_gbuffer: invalid tiling");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    {
+        // the last local row must map into the image
+        uint32_t l = T.local_rows - 1, band = l / T.band_rows, within = l % T.band_rows;
+        uint64_t g = ((uint64_t)band * T.num_ranks + T.rank) * T.band_rows + within;
+        if (g >= a->height) { set_error("rt_gbuffer: tiling maps local rows outside the image"); return RT_ERR_INVALID_ARGUMENT; }
+    }
+    const DeviceScene& S = scene->dev;
+    if (S.wide_refs) { set_error("rt_gbuffer: scenes with 32-bit references are not supported"); return RT_ERR_UNSUPPORTED; }
+    // the scenes rt_render's automatic choice gives to the flat kernels
+    const bool flat = S.prims_flat && S.flat_source && S.num_prims <= (uint32_t)g_flat_max;
+    const size_t lds = flat ? 0 : (size_t)(S.depth + 2) * 64 * 2;
+    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_gbuffer: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    dev::GBufParams G;
+    std::memset(&G, 0, sizeof(G));
+    dev::KParams& P = G.K;
+    P.nodes48 = (const float4*)S.nodes48;
+    P.refs = (const uint32_t*)S.refs;
+    P.prims = (const float4*)(flat ? S.prims_flat : S.prims);
+    P.mats = (const float4*)S.mats;
+    P.imgs = (const int4*)S.imgs;
+    P.texels = (const uint8_t*)S.texels;
+    P.num_nodes = S.num_nodes;
+    P.num_prims = S.num_prims;
+    P.num_mats = S.num_mats;
+    P.num_imgs = S.num_imgs;
+    P.width = a->width;
+    P.height = a->height;
+    P.band_rows = T.band_rows;
+    P.num_ranks = T.num_ranks;
+    P.rank = T.rank;
+    P.local_rows = T.local_rows;
+    P.grid_w = a->width;
+    P.grid_h = a->height;
+    P.leaf_break = (uint32_t)g_leaf_break;
+    if (flat) {
+        P.ref_nodes = (const float4*)S.ref_nodes;
+        P.flat_boxes = (const float4*)S.flat_boxes;
+        P.flat_runs[0] = S.flat_runs[0];
+        P.flat_runs[1] = S.flat_runs[1];
+    }
+    fill_camera(P, a->inputs, a->width, a->height);
+    P.tiles_x = (a->width + 7u) / 8u;
+    const uint64_t tiles = (uint64_t)P.tiles_x * ((T.local_rows + 7u) / 8u);
+    if (tiles > 0x7fffffffull) { set_error("rt_gbuffer: frame too large"); return RT_ERR_INVALID_ARGUMENT; }
+    G.normal_depth = (float4*)a->normal_depth;
+    G.albedo = (float4*)a->albedo;
+    G.prim_id = a->prim_id;
+    G.source = (const int32_t*)(flat ? S.flat_source : S.prim_source);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    if (flat)
+        hipLaunchKernelGGL(dev::gbuffer_kernel<true>, dim3((uint32_t)tiles), dim3(64), 0, s, G);
+    else
+        hipLaunchKernelGGL(dev::gbuffer_kernel<false>, dim3((uint32_t)tiles), dim3(64), lds, s, G);
+    return hip_check(hipGetLastError(), "rt_gbuffer: kernel launch", RT_ERR_LAUNCH);
 }
 
 int rt_set_pixel_cost(void* buffer, uint64_t bytes) {
@@ -4234,41 +4464,7 @@ int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) 
     P.ray_dump_count = g_ray_dump_count;
     P.ray_dump_cap = g_ray_dump_cap;
     P.ray_dump_depth = g_ray_dump_depth;
-    // Launch-uniform camera terms, with the binary32 operations of Kernel.cu:130-143.
-    const rt_input_struct& in = a->inputs;
-    P.width_f = (float)a->width;
-    P.inv_width = 1.0f / P.width_f;
-    P.cx = (float)a->width / 2.0f;
-    P.cy = (float)a->height / 2.0f;
-    P.near_plane = in.near_plane;
-    P.far_plane = in.far_plane;
-    {
-        volatile float up[3] = {in.up[0], in.up[1], in.up[2]};
-        volatile float fw[3] = {in.orientation[0], in.orientation[1], in.orientation[2]};
-        // rightV = Normalize(Cross(upV, forwardV)) (Kernel.cu:133, Math.cuh:157-161, 225-229)
-        volatile float cx = up[1] * fw[2] - up[2] * fw[1];
-        volatile float t = up[0] * fw[2] - up[2] * fw[0];
-        volatile float cy = -t;
-        volatile float cz = up[0] * fw[1] - up[1] * fw[0];
-        volatile float d0 = cx * cx, d1 = cy * cy, d2 = cz * cz;
-        volatile float dd = d0 + d1;
-        dd = dd + d2;
-        volatile float s = std::sqrt((float)dd);
-        volatile float inv = 1.0f / s;
-        P.right[0] = inv * cx;
-        P.right[1] = inv * cy;
-        P.right[2] = inv * cz;
-        volatile float k10 = 1.0f / in.fov;
-        k10 = k10 * 10.0f;
-        for (int i = 0; i < 3; i++) {
-            P.origin[i] = in.origin[i];
-            P.up[i] = in.up[i];
-            P.fov_fwd[i] = in.fov * fw[i];
-            P.k10_fwd[i] = k10 * fw[i];
-            P.bg0[i] = in.background_start[i];
-            P.bg1[i] = in.background_end[i];
-        }
-    }
+    fill_camera(P, a->inputs, a->width, a->height);
 
     const bool count_tests = a->counters && (a->flags & RT_FLAG_COUNT_TESTS);
     int variant = g_variant;

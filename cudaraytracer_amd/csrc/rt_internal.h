@@ -76,6 +76,7 @@ struct HostScene {
     std::vector<int32_t> prim_source;  // desc index of each primitive (BVH order)
     std::vector<float> prims_flat;     // scenes of <= kFlatMaxPrims primitives: the records in the reference BVH's
                                        // test order (the flat kernel's table), else empty
+    std::vector<int32_t> flat_source;  // ... and the desc index of each flat record (rt_gbuffer's prim_id)
     std::vector<float> ref_nodes;      // ... and the reference BVH itself: 8 floats per node (scene_build.cpp)
     std::vector<float> flat_ref_pairs; // ... and the same tree as child-pair records (16 floats per node)
     std::vector<float> flat_boxes;     // ... and per flat record its reference box for the flat kernels' exactness

@@ -22,6 +22,8 @@ struct DeviceScene {
     const void* bvh_boxes = nullptr;      // per `prims` record its reference box, or NULL
     const void* bvh_ref_pairs = nullptr;  // per reference node its children's boxes and references (ref_trace_wave)
     uint32_t flat_runs[2] = {0u, 0u};  // HostScene::flat_runs
+    const void* prim_source = nullptr;  // per `prims` record the index of its hittable in the caller's description
+    const void* flat_source = nullptr;  // ... per prims_flat record, or NULL (rt_gbuffer's prim_id)
     const void* mats = nullptr;    // float4 × 3 per material
     const void* imgs = nullptr;    // int4 per image
     const void* texels = nullptr;  // RGB8

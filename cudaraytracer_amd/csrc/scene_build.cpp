@@ -637,6 +637,7 @@ int build_host_scene(const rt_scene_desc* desc, HostScene* out, std::string* err
             std::vector<int> flat_index(desc->num_hittables, -1);
             out->prims_flat.resize(ord.size() * 8);
             out->flat_boxes.resize(ord.size() * 8);
+            out->flat_source.assign(ord.begin(), ord.end());
             for (size_t i = 0; i < ord.size(); i++) {
                 flat_index[ord[i]] = (int)i;
                 pack_prim(desc->hittables[ord[i]], out->prims_flat.data() + i * 8);
@@ -663,6 +664,7 @@ int build_host_scene(const rt_scene_desc* desc, HostScene* out, std::string* err
             if (!contiguous) {
                 out->prims_flat.clear();
                 out->flat_boxes.clear();
+                out->flat_source.clear();
                 out->flat_runs[0] = out->flat_runs[1] = 0u;
                 return RT_OK;
             }

@@ -99,6 +99,10 @@ class Renderer:
         self.radiance = None
         self.accum = None
         self._accum_restart = False  # the next accumulating frame restarts the sums (RT_FLAG_ACCUMULATE_RESET)
+        self.normal_depth = self.albedo = self.prim_id = None  # gbuffer(): allocated on first use
+        self.denoised = None          # denoise(): the float result (local_rows × W × 4)
+        self._denoise_scratch = None  # ... its ping-pong planes, allocated once
+        self._denoise_pos = None
 
     def tiling(self) -> abi.Tiling:
         return abi.Tiling(self.band_rows, self.num_ranks, self.rank, self.local_rows)
@@ -159,6 +163,62 @@ class Renderer:
         """Restart the progressive sums (camera move, scene edit): the next accumulating frame passes
         RT_FLAG_ACCUMULATE_RESET, which writes the accumulator without reading it — no fill kernel."""
         self._accum_restart = True
+
+    def gbuffer(self, scene: DeviceScene, inputs: abi.InputStruct):
+        """First-hit G-buffer of this rank's rows (rt_gbuffer), asynchronous on torch's current stream: returns
+        (normal_depth (rows, W, 4) float32, albedo (rows, W, 4) float32, prim_id (rows, W) int32), cached on the
+        renderer.  No RNG draw: the states are untouched."""
+        if self.normal_depth is None:
+            shape = (self.local_rows, self.width)
+            self.normal_depth = torch.zeros(shape + (4,), dtype=torch.float32, device=self.device)
+            self.albedo = torch.zeros(shape + (4,), dtype=torch.float32, device=self.device)
+            self.prim_id = torch.zeros(shape, dtype=torch.int32, device=self.device)
+        a = abi.GBufferArgs()
+        a.normal_depth, a.albedo, a.prim_id = self.normal_depth.data_ptr(), self.albedo.data_ptr(), self.prim_id.data_ptr()
+        a.width, a.height = self.width, self.height
+        a.tiling = self.tiling()
+        a.inputs = inputs
+        check(lib().rt_gbuffer(scene.handle, C.byref(a), C.c_void_p(self.stream())), "rt_gbuffer")
+        return self.normal_depth, self.albedo, self.prim_id
+
+    def denoise(self, iterations: int = 3, sigma_c: float = 0.6, sigma_n: float = 0.1, sigma_z: float = 0.05,
+                demodulate: bool = True, source: str = "radiance") -> np.ndarray:
+        """Edge-avoiding à-trous filter (rt_denoise) of the last frame's `radiance` (render(..., radiance=True)) or
+        `accum` (RT_FLAG_ACCUMULATE) plane, guided by the last gbuffer(); whole frames only (num_ranks = 1).  Returns
+        the RGBA8 image like image() and keeps the float result in `self.denoised`."""
+        pos = self.denoise_async(iterations, sigma_c, sigma_n, sigma_z, demodulate, source)
+        return pos.cpu().numpy().view(np.uint32).reshape(self.local_rows, self.width)
+
+    def denoise_async(self, iterations: int = 3, sigma_c: float = 0.6, sigma_n: float = 0.1, sigma_z: float = 0.05,
+                      demodulate: bool = True, source: str = "radiance") -> torch.Tensor:
+        """denoise() without the copy to the host: asynchronous on torch's current stream; returns the device RGBA8
+        framebuffer (as render() returns `pos`)."""
+        if source not in ("radiance", "accum"):
+            raise ValueError(f"source must be 'radiance' or 'accum', not {source!r}")
+        color = self.radiance if source == "radiance" else self.accum
+        if color is None:
+            raise RTError(f"denoise: no {source} plane (render with radiance=True / RT_FLAG_ACCUMULATE first)")
+        if self.normal_depth is None:
+            raise RTError("denoise: no G-buffer (call gbuffer() first)")
+        L = lib()
+        n = self.width * self.local_rows
+        if self.denoised is None:
+            self.denoised = torch.zeros((self.local_rows, self.width, 4), dtype=torch.float32, device=self.device)
+            self._denoise_pos = torch.zeros(n, dtype=torch.int32, device=self.device)
+        need = int(L.rt_denoise_scratch_bytes(self.width, self.height, 6))  # once, for any iteration count
+        if self._denoise_scratch is None and need:
+            self._denoise_scratch = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        a = abi.DenoiseArgs()
+        a.color = color.data_ptr()
+        a.normal_depth, a.albedo, a.prim_id = self.normal_depth.data_ptr(), self.albedo.data_ptr(), self.prim_id.data_ptr()
+        a.out_color, a.pos = self.denoised.data_ptr(), self._denoise_pos.data_ptr()
+        a.scratch = self._denoise_scratch.data_ptr() if self._denoise_scratch is not None else None
+        a.width, a.height, a.iterations = self.width, self.height, iterations
+        a.flags = (abi.RT_DENOISE_DEMODULATE if demodulate else 0) | (abi.RT_DENOISE_COLOR_IS_SUM if source == "accum" else 0)
+        a.sigma_c, a.sigma_n, a.sigma_z = sigma_c, sigma_n, sigma_z
+        a.tiling = self.tiling()
+        check(L.rt_denoise(C.byref(a), C.c_void_p(self.stream())), "rt_denoise")
+        return self._denoise_pos
 
     def image(self) -> np.ndarray:
         """Local framebuffer as (local_rows, W) uint32 RGBA8 (row 0 = bottom of the image)."""

@@ -181,8 +181,9 @@ const char* rt_last_error(void);
 const char* rt_version(void);
 
 /* Version of this C ABI (structure layouts, counter words, entry points); a caller built against an older header
- * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags. */
-#define RT_ABI_VERSION 6
+ * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
+ * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes. */
+#define RT_ABI_VERSION 7
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -351,6 +352,85 @@ int rt_set_ray_dump(void* rays, uint32_t capacity, uint32_t* count, uint32_t dep
  * `stream`.  Scenes with 32-bit references are not supported (RT_ERR_UNSUPPORTED). */
 int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t* hits, uint64_t* counters,
                   int count_tests, rt_stream stream);
+
+/* ------------------------------------------------------------------------------------------------ */
+/* First-hit G-buffer and edge-avoiding denoiser for low-spp frames.  The reference has neither: while */
+/* the camera moves its viewer shows the raw frame of LaunchKernel (CudaLayer.cpp:372-386).  A viewer   */
+/* calls both between rt_render / LaunchKernel and the GL copy.                      */
+/* ------------------------------------------------------------------------------------------------ */
+
+/* What the camera ray through each pixel's centre hits: the ray of Kernel.cu:139-146 with both jitter numbers
+ * fixed at 0.5 (no RNG draw; the RNG state is neither read nor written), closest hit with rt_trace_rays'
+ * semantics (BVHNode::Hit, t in (0.001, FLT_MAX); the geometric closest hit, no reference replay), hit record
+ * (point, normal, u, v, texture value) as the render kernels derive it.  Buffers are device memory of
+ * local_rows × width elements, row 0 at the bottom; each is optional, at least one must be given:
+ *   normal_depth  float4: xyz = the HitRecord normal (sphere (p - c) / r, not face-flipped; rectangles
+ *                 face-flipped, Hittable.cuh:23-27), w = t.  Miss: (0, 0, 0, -1).
+ *   albedo        float4, w = 1: Lambertian / Metal the albedo texture's value at the hit, Dielectric (1, 1, 1),
+ *                 DiffuseLight light_intensity · texture.  Miss: the sky colour of color() (Kernel.cu:41-44).
+ *   prim_id       int32: the hit hittable's index in rt_scene_desc.hittables (inactive entries counted; for
+ *                 rt_scene_from_reference_graph scenes the order of rt_reference_graph_flatten).  Miss: -1.
+ *                 At the cursor's pixel this is an object pick.
+ * A band render's rows equal the whole-frame rows (rt_tiling, as rt_render).  Scenes with 32-bit BVH references
+ * are not supported (RT_ERR_UNSUPPORTED, as rt_trace_rays). */
+typedef struct rt_gbuffer_args {
+    float* normal_depth;
+    float* albedo;
+    int32_t* prim_id;
+    uint32_t width;
+    uint32_t height;      /* global image height */
+    uint32_t reserved[2]; /* must be 0 */
+    rt_tiling tiling;
+    rt_input_struct inputs;
+} rt_gbuffer_args;
+
+/* One G-buffer pass on `stream`, asynchronous; status codes and rt_last_error as rt_render. */
+int rt_gbuffer(const rt_scene* scene, const rt_gbuffer_args* args, rt_stream stream);
+
+enum rt_denoise_flags {
+    RT_DENOISE_DEMODULATE = 1u << 0,   /* filter colour / max(albedo, 1/256) and multiply it back at the end: texture
+                                          detail is not blurred */
+    RT_DENOISE_COLOR_IS_SUM = 1u << 1  /* `color` is rt_render_args.accum: colour = rgb / w, 0 where w = 0 */
+};
+
+/* Edge-avoiding à-trous wavelet filter (Dammertz et al. 2010) of a whole frame, guided by rt_gbuffer's planes.
+ * With c_0 = colour (RT_DENOISE_DEMODULATE: colour / max(albedo, 1/256) per channel), iteration i = 0 .. N-1 with
+ * step s = 2^i computes for every pixel p with prim_id(p) >= 0
+ *   c_{i+1}(p) = Σ_q w·c_i(q) / Σ_q w   over q = p + s·(dx, dy), dx, dy in -2..2, inside the frame, prim_id(q) >= 0,
+ *   w = h[dx+2]·h[dy+2]·expf(-(e_n + e_z + e_c)),  h = (1/16, 1/4, 3/8, 1/4, 1/16),
+ *   e_n = max(0, 1 - n_p·n_q) / sigma_n,  e_z = |t_p - t_q| / (sigma_z · max(t_p, 1e-3)),
+ *   e_c = |c_i(p) - c_i(q)|² / (sigma_c · 2^-i)²;
+ * a pixel with prim_id(p) < 0 (a miss: sky) passes through, c_{i+1}(p) = c_i(p).  The result (RT_DENOISE_DEMODULATE:
+ * times the same max(albedo, 1/256)) goes to out_color (rgb, w = 1) and / or, through the render kernels' epilogue
+ * (255·sqrtf, clamp, truncate, alpha 255: Kernel.cu:12-19, 152-157), to pos.  Defaults worth starting from: iterations
+ * 3, sigma_c 0.6, sigma_n 0.1, sigma_z 0.05.
+ * One kernel launch per iteration, no atomics: two calls on the same inputs give the same bits.  Intermediate colour
+ * ping-pongs in `scratch` (device memory of rt_denoise_scratch_bytes bytes; may be NULL when that is 0).  Buffers are
+ * height × width elements, row 0 at the bottom.  out_color, pos and scratch must not overlap any input (an
+ * iteration's taps read pixels other workgroups write): out_color aliasing color is rejected
+ * (RT_ERR_INVALID_ARGUMENT).  The filter's taps cross band boundaries, so it works on a whole frame only: a tiling
+ * with num_ranks > 1 is rejected. */
+typedef struct rt_denoise_args {
+    const float* color;        /* float4 per pixel: rt_render_args.radiance (RT_DENOISE_COLOR_IS_SUM: .accum) */
+    const float* normal_depth; /* rt_gbuffer_args.normal_depth */
+    const float* albedo;       /* rt_gbuffer_args.albedo */
+    const int32_t* prim_id;    /* rt_gbuffer_args.prim_id */
+    float* out_color;          /* optional float4 per pixel */
+    uint32_t* pos;             /* optional RGBA8 framebuffer (at least one output) */
+    void* scratch;
+    uint32_t width;
+    uint32_t height;
+    uint32_t iterations;       /* N, 1..6 */
+    uint32_t flags;            /* rt_denoise_flags */
+    float sigma_c, sigma_n, sigma_z; /* all > 0 */
+    uint32_t reserved;         /* must be 0 */
+    rt_tiling tiling;          /* {band_rows = height, num_ranks = 1, rank = 0, local_rows = height} */
+} rt_denoise_args;
+
+/* Bytes of rt_denoise_args.scratch for a frame (0 for an empty frame or a single iteration). */
+uint64_t rt_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t iterations);
+/* The filter on `stream`, asynchronous; status codes and rt_last_error as rt_render. */
+int rt_denoise(const rt_denoise_args* args, rt_stream stream);
 
 /* Tuning/benchmark knob (per thread): the kernel rt_render launches.  -1 = automatic: 3 from 64 spp; below,
  * the faster of 3 and 4 as timed on the first frames of each (device, stream, scene, frame shape, spp, depth,

@@ -1,0 +1,74 @@
+"""Cost of the G-buffer pass and the denoiser next to the frame they serve: BASELINE config 5 (1920x1080, 1 spp, depth
+4, textured spheres, moving camera, accumulation restarted every frame) on one GPU.
+
+Times rt_render, rt_gbuffer and rt_denoise (N = 1, 3, 5; defaults otherwise; colour read from the accumulator,
+RT_DENOISE_COLOR_IS_SUM, demodulated) separately with HIP events: warm-up frames, then the median over --frames frames
+of the scripted camera orbit.  Prints one JSON line: ms, the compulsory bytes of each pass (per filter iteration one
+colour plane read and one written and the normal/depth plane read, 16 B per pixel each; the first iteration also reads
+prim_id, 4 B, and the albedo, 16 B; the last reads the albedo and writes the RGBA8 framebuffer, 4 B; the G-buffer pass
+writes its 36 B per pixel) and the GB/s they amount to, and each pass's ratio to the render time of the same run.
+"""
+import argparse, json, os, statistics, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from cudaraytracer_amd import abi, scenes
+from cudaraytracer_amd.renderer import DeviceScene, Renderer
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--frames", type=int, default=120, help="timed frames (the median is reported)")
+ap.add_argument("--warmup", type=int, default=12)
+ap.add_argument("--width", type=int, default=0, help="override the config's size (with --height)")
+ap.add_argument("--height", type=int, default=0)
+ap.add_argument("--texture-size", default="", help="WxH of the three textures (default: the config's 8192x4096)")
+args = ap.parse_args()
+
+cfg = scenes.CONFIGS["c5"]
+if args.width and args.height:
+    cfg = cfg.scaled(args.width, args.height)
+if args.texture_size:
+    cfg.texture_size = tuple(int(v) for v in args.texture_size.split("x"))
+ds = DeviceScene(cfg.scene_desc())
+r = Renderer(cfg.width, cfg.height)
+r.render_init()
+ITER = (1, 3, 5)
+npix = cfg.width * cfg.height
+
+
+def denoise_bytes(n: int) -> int:
+    return npix * (n * 48 + 4 + 16 + 16 + 4)
+
+
+def timed(fn) -> float:
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1)
+
+
+times = {"render": [], "gbuffer": [], **{f"denoise_n{n}": [] for n in ITER}}
+total = args.warmup + args.frames
+for f in range(total):
+    pos, fwd = scenes.moving_camera(f % 60, 60)
+    inp = scenes.camera_inputs(pos, fwd, cfg.fov)
+    r.reset_accumulation()
+    t = {"render": timed(lambda: r.render(ds, cfg.spp, cfg.depth, inp, flags=abi.RT_FLAG_ACCUMULATE, count=False)),
+         "gbuffer": timed(lambda: r.gbuffer(ds, inp))}
+    for n in ITER:
+        t[f"denoise_n{n}"] = timed(lambda: r.denoise_async(iterations=n, source="accum"))
+    if f >= args.warmup:
+        for k, v in t.items():
+            times[k].append(v)
+
+ms = {k: statistics.median(v) for k, v in times.items()}
+out = {"config": "c5", "workload": f"{cfg.width}x{cfg.height}, {cfg.spp} spp, depth {cfg.depth}", "frames": args.frames,
+       "warmup": args.warmup, "device": torch.cuda.get_device_name(0), "render_ms": round(ms["render"], 4)}
+gb = npix * 36
+out["gbuffer"] = {"ms": round(ms["gbuffer"], 4), "bytes": gb, "GB_per_s": round(gb / ms["gbuffer"] / 1e6, 1),
+                  "ratio_to_render": round(ms["gbuffer"] / ms["render"], 3)}
+for n in ITER:
+    m, b = ms[f"denoise_n{n}"], denoise_bytes(n)
+    out[f"denoise_n{n}"] = {"ms": round(m, 4), "bytes": b, "GB_per_s": round(b / m / 1e6, 1),
+                            "ms_per_iteration": round(m / n, 4), "ratio_to_render": round(m / ms["render"], 3)}
+print(json.dumps(out), flush=True)

@@ -49,6 +49,7 @@ EXPORTED = [
     "rt_gbuffer",
     "rt_denoise",
     "rt_denoise_scratch_bytes",
+    "rt_temporal",
     "rt_last_kernel_ms",
     "rt_last_variant",
     "rt_last_launch_host_ms",
@@ -105,6 +106,7 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_denoise.argtypes = [P(abi.DenoiseArgs), vp]
     lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     lib.rt_denoise_scratch_bytes.restype = C.c_uint64
+    lib.rt_temporal.argtypes = [P(abi.TemporalArgs), vp]
     lib.rt_last_kernel_ms.restype = C.c_float
     lib.rt_last_variant.restype = C.c_int
     lib.rt_last_launch_host_ms.restype = C.c_float

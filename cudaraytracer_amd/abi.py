@@ -24,6 +24,8 @@ RT_FLAG_STATE_SOA = 1 << 6
 RT_FLAG_ACCUMULATE_RESET = 1 << 7
 RT_DENOISE_DEMODULATE = 1 << 0
 RT_DENOISE_COLOR_IS_SUM = 1 << 1
+RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
+RT_TEMPORAL_RESET = 1 << 1
 COUNTERS_WORDS = 24  # RT_COUNTERS_WORDS: the counters buffer with RT_FLAG_COUNT_TESTS
 PHILOX_MAX_SPP = 16384  # RT_PHILOX_MAX_SPP
 # rt_set_tuning keys (rt_tuning_key in include/rt_hip.h)
@@ -193,6 +195,30 @@ class DenoiseArgs(C.Structure):
         ("sigma_z", C.c_float),
         ("reserved", C.c_uint32),
         ("tiling", Tiling),
+    ]
+
+
+class TemporalArgs(C.Structure):
+    _fields_ = [
+        ("color", C.c_void_p),
+        ("normal_depth", C.c_void_p),
+        ("prim_id", C.c_void_p),
+        ("prev_history", C.c_void_p),
+        ("prev_normal_depth", C.c_void_p),
+        ("prev_prim_id", C.c_void_p),
+        ("history", C.c_void_p),
+        ("motion", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("max_history", C.c_uint32),
+        ("depth_tol", C.c_float),
+        ("normal_tol", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+        ("tiling", Tiling),
+        ("inputs", InputStruct),
+        ("prev_inputs", InputStruct),
     ]
 
 

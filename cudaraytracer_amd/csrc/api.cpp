@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <new>
 #include <stdexcept>
 #include <cstring>
@@ -503,6 +504,91 @@ int rt_build_host_tables(const rt_scene_desc* desc, float* nodes, float* prims, 
     if (materials) std::copy(h.mats.begin(), h.mats.end(), materials);
     if (prim_source) std::copy(h.prim_source.begin(), h.prim_source.end(), prim_source);
     return RT_OK;
+}
+
+// A camera's launch-uniform terms (Kernel.cu:130-143; the library is compiled with -ffp-contract=off, so every
+// operation below is one binary32 rounding, as in render.hip's fill_camera).
+static TemporalCamera temporal_camera(const rt_input_struct& in) {
+    TemporalCamera c;
+    const float* up = in.up;
+    const float* fw = in.orientation;
+    // rightV = Normalize(Cross(upV, forwardV)) (Kernel.cu:133, Math.cuh:157-161, 225-229)
+    const float cx = up[1] * fw[2] - up[2] * fw[1];
+    const float cy = -(up[0] * fw[2] - up[2] * fw[0]);
+    const float cz = up[0] * fw[1] - up[1] * fw[0];
+    const float inv = 1.0f / std::sqrt((cx * cx + cy * cy) + cz * cz);
+    c.right[0] = inv * cx;
+    c.right[1] = inv * cy;
+    c.right[2] = inv * cz;
+    c.fov = in.fov;
+    c.k10 = (1.0f / in.fov) * 10.0f;
+    c.near_plane = in.near_plane;
+    c.far_plane = in.far_plane;
+    for (int i = 0; i < 3; i++) {
+        c.origin[i] = in.origin[i];
+        c.fw[i] = fw[i];
+        c.up[i] = up[i];
+        c.fov_fwd[i] = in.fov * fw[i];
+        c.k10_fwd[i] = c.k10 * fw[i];
+    }
+    c.fw_dot_fw = (fw[0] * fw[0] + fw[1] * fw[1]) + fw[2] * fw[2];
+    return c;
+}
+
+int rt_temporal(const rt_temporal_args* a, rt_stream stream) {
+    // (every check runs before the first device call)
+    const auto bad = [](const char* msg) {
+        set_error(std::string("rt_temporal: ") + msg);
+        return (int)RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!a) return bad("NULL args");
+    if (a->reserved[0] != 0 || a->reserved[1] != 0) return bad("reserved fields must be 0");
+    if (a->flags & ~(uint32_t)(RT_TEMPORAL_COLOR_IS_SUM | RT_TEMPORAL_RESET)) return bad("unknown flags");
+    if (a->max_history < 1 || a->max_history > 4096) return bad("max_history must be 1..4096");
+    if (!(a->depth_tol > 0.0f) || !(a->normal_tol > 0.0f)) return bad("depth_tol and normal_tol must be > 0");
+    if (a->tiling.num_ranks > 1) return bad("the pass works on a whole frame (tiling.num_ranks > 1)");
+    if (a->tiling.local_rows != 0 && a->tiling.local_rows != a->height) return bad("tiling.local_rows is not the frame's height");
+    if (!a->color || !a->normal_depth || !a->prim_id) return bad("NULL input plane");
+    if (!a->history) return bad("NULL history (the output plane)");
+    const bool reset = (a->flags & RT_TEMPORAL_RESET) != 0;
+    if (!reset && (!a->prev_history || !a->prev_normal_depth || !a->prev_prim_id))
+        return bad("NULL prev_* plane without RT_TEMPORAL_RESET");
+    const uint64_t n = (uint64_t)a->width * a->height;
+    if (n > 0x7fffffffull) return bad("frame too large");
+    if (!reset) {  // (with RT_TEMPORAL_RESET nothing is gathered)
+        const void* outs[3] = {a->history, a->motion, a->pos};
+        const uint64_t out_bytes[3] = {n * 16u, n * 8u, n * 4u};
+        const void* prevs[3] = {a->prev_history, a->prev_normal_depth, a->prev_prim_id};
+        const uint64_t prev_bytes[3] = {n * 16u, n * 16u, n * 4u};
+        for (int o = 0; o < 3; o++)
+            for (int i = 0; i < 3; i++)
+                if (overlaps(outs[o], out_bytes[o], prevs[i], prev_bytes[i]))
+                    return bad(o == 0 && i == 0 ? "history must not alias prev_history (ping-pong two planes)"
+                                                : "an output overlaps a prev_* plane");
+    }
+    if (n == 0) return RT_OK;
+    TemporalParams P{};
+    P.color = a->color;
+    P.normal_depth = a->normal_depth;
+    P.prim_id = a->prim_id;
+    P.prev_history = reset ? nullptr : a->prev_history;
+    P.prev_normal_depth = reset ? nullptr : a->prev_normal_depth;
+    P.prev_prim_id = reset ? nullptr : a->prev_prim_id;
+    P.history = a->history;
+    P.motion = a->motion;
+    P.pos = a->pos;
+    P.width = a->width;
+    P.height = a->height;
+    P.flags = a->flags;
+    P.max_history = (float)a->max_history;
+    P.depth_tol = a->depth_tol;
+    P.min_ndot = 1.0f - a->normal_tol;
+    P.width_f = (float)a->width;
+    P.half_w = (float)a->width / 2.0f;
+    P.half_h = (float)a->height / 2.0f;
+    P.cur = temporal_camera(a->inputs);
+    P.prev = reset ? P.cur : temporal_camera(a->prev_inputs);  // (prev_inputs is not read with RT_TEMPORAL_RESET)
+    return launch_temporal(P, stream);
 }
 
 int rt_scene_destroy(rt_scene* scene) {

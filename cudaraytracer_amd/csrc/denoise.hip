@@ -194,12 +194,6 @@ uint64_t rt_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t iter
     return (uint64_t)width * height * 16u * scratch_planes(iterations);
 }
 
-static bool overlaps(const void* a, const uint64_t na, const void* b, const uint64_t nb) {
-    if (!a || !b || na == 0 || nb == 0) return false;
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + nb && pb < pa + na;
-}
-
 int rt_denoise(const rt_denoise_args* a, rt_stream stream) {
     const auto bad = [](const char* msg) {
         set_error(std::string("rt_denoise: ") + msg);

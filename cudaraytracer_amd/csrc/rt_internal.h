@@ -118,6 +118,40 @@ int flatten_reference_graph(const void* world, FlatDesc* out, std::string* err);
 
 void set_error(const std::string& msg);
 
+// Do the byte ranges [a, a + na) and [b, b + nb) share a byte?  (A NULL or empty range shares none.)
+inline bool overlaps(const void* a, const uint64_t na, const void* b, const uint64_t nb) {
+    if (!a || !b || na == 0 || nb == 0) return false;
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+
+// rt_temporal (api.cpp validates and fills, temporal.hip launches).  A camera's launch-uniform terms with the binary32
+// operations of Kernel.cu:130-143, as rt_render / rt_gbuffer build them.
+struct TemporalCamera {
+    float origin[3], fw[3], up[3], right[3];
+    float fov_fwd[3];  // fov · fw
+    float k10_fwd[3];  // ((1 / fov) · 10) · fw
+    float fov, k10, near_plane, far_plane;
+    float fw_dot_fw;
+};
+struct TemporalParams {
+    const float* color;
+    const float* normal_depth;
+    const int32_t* prim_id;
+    const float* prev_history;
+    const float* prev_normal_depth;
+    const int32_t* prev_prim_id;
+    float* history;
+    float* motion;
+    uint32_t* pos;
+    uint32_t width, height, flags;
+    float max_history, depth_tol, min_ndot;  // min_ndot = 1 − normal_tol
+    float width_f, half_w, half_h;           // W, W / 2, H / 2
+    TemporalCamera cur, prev;
+};
+// One launch on `stream` (a hipStream_t); RT_OK or RT_ERR_LAUNCH with the error set.
+int launch_temporal(const TemporalParams& P, void* stream);
+
 inline float bits_to_float(uint32_t u) {
     float f;
     static_assert(sizeof(f) == sizeof(u), "");

@@ -103,6 +103,13 @@ class Renderer:
         self.denoised = None          # denoise(): the float result (local_rows × W × 4)
         self._denoise_scratch = None  # ... its ping-pong planes, allocated once
         self._denoise_pos = None
+        # gbuffer(keep_previous=True): the frame before's planes and camera; temporal(): the accumulated colour
+        self.prev_normal_depth = self.prev_prim_id = self.prev_inputs = None
+        self._gbuffer_inputs = None
+        self.history = None          # temporal(): (local_rows × W × 4) float32, rgb + history length
+        self._history_spare = None   # ... the plane the next call writes (the two ping-pong)
+        self.motion = None           # temporal(motion=True): (local_rows × W × 2) float32
+        self._temporal_pos = None
 
     def tiling(self) -> abi.Tiling:
         return abi.Tiling(self.band_rows, self.num_ranks, self.rank, self.local_rows)
@@ -164,10 +171,19 @@ class Renderer:
         RT_FLAG_ACCUMULATE_RESET, which writes the accumulator without reading it — no fill kernel."""
         self._accum_restart = True
 
-    def gbuffer(self, scene: DeviceScene, inputs: abi.InputStruct):
+    def gbuffer(self, scene: DeviceScene, inputs: abi.InputStruct, keep_previous: bool = False):
         """First-hit G-buffer of this rank's rows (rt_gbuffer), asynchronous on torch's current stream: returns
         (normal_depth (rows, W, 4) float32, albedo (rows, W, 4) float32, prim_id (rows, W) int32), cached on the
-        renderer.  No RNG draw: the states are untouched."""
+        renderer.  No RNG draw: the states are untouched.  keep_previous: write into the renderer's second plane set,
+        so the planes and camera of the call before stay available as prev_normal_depth, prev_prim_id and prev_inputs
+        (what temporal() reprojects into); the default overwrites the one set in place."""
+        if keep_previous and self.normal_depth is not None:
+            spare_nd = self.prev_normal_depth if self.prev_normal_depth is not None else torch.zeros_like(self.normal_depth)
+            spare_id = self.prev_prim_id if self.prev_prim_id is not None else torch.zeros_like(self.prim_id)
+            self.prev_normal_depth, self.normal_depth = self.normal_depth, spare_nd
+            self.prev_prim_id, self.prim_id = self.prim_id, spare_id
+            self.prev_inputs = self._gbuffer_inputs
+        self._gbuffer_inputs = abi.InputStruct.from_buffer_copy(inputs)
         if self.normal_depth is None:
             shape = (self.local_rows, self.width)
             self.normal_depth = torch.zeros(shape + (4,), dtype=torch.float32, device=self.device)
@@ -184,7 +200,8 @@ class Renderer:
     def denoise(self, iterations: int = 3, sigma_c: float = 0.6, sigma_n: float = 0.1, sigma_z: float = 0.05,
                 demodulate: bool = True, source: str = "radiance") -> np.ndarray:
         """Edge-avoiding à-trous filter (rt_denoise) of the last frame's `radiance` (render(..., radiance=True)) or
-        `accum` (RT_FLAG_ACCUMULATE) plane, guided by the last gbuffer(); whole frames only (num_ranks = 1).  Returns
+        `accum` (RT_FLAG_ACCUMULATE) plane, or of temporal()'s `history` (source="history"), guided by the last
+        gbuffer(); whole frames only (num_ranks = 1).  Returns
         the RGBA8 image like image() and keeps the float result in `self.denoised`."""
         pos = self.denoise_async(iterations, sigma_c, sigma_n, sigma_z, demodulate, source)
         return pos.cpu().numpy().view(np.uint32).reshape(self.local_rows, self.width)
@@ -193,11 +210,12 @@ class Renderer:
                       demodulate: bool = True, source: str = "radiance") -> torch.Tensor:
         """denoise() without the copy to the host: asynchronous on torch's current stream; returns the device RGBA8
         framebuffer (as render() returns `pos`)."""
-        if source not in ("radiance", "accum"):
-            raise ValueError(f"source must be 'radiance' or 'accum', not {source!r}")
-        color = self.radiance if source == "radiance" else self.accum
+        if source not in ("radiance", "accum", "history"):
+            raise ValueError(f"source must be 'radiance', 'accum' or 'history', not {source!r}")
+        color = {"radiance": self.radiance, "accum": self.accum, "history": self.history}[source]
         if color is None:
-            raise RTError(f"denoise: no {source} plane (render with radiance=True / RT_FLAG_ACCUMULATE first)")
+            raise RTError(f"denoise: no {source} plane (render with radiance=True / RT_FLAG_ACCUMULATE, or call "
+                          "temporal(), first)")
         if self.normal_depth is None:
             raise RTError("denoise: no G-buffer (call gbuffer() first)")
         L = lib()
@@ -219,6 +237,49 @@ class Renderer:
         a.tiling = self.tiling()
         check(L.rt_denoise(C.byref(a), C.c_void_p(self.stream())), "rt_denoise")
         return self._denoise_pos
+
+    def temporal(self, max_history: int = 32, depth_tol: float = 0.05, normal_tol: float = 0.2,
+                 source: str = "radiance", reset: bool = False, motion: bool = False) -> torch.Tensor:
+        """Reprojected temporal accumulation (rt_temporal) of the last frame's `radiance` or `accum` plane into
+        `self.history` (rows, W, 4: rgb, history length), asynchronous on torch's current stream; whole frames only.
+        Call once per frame after render() and gbuffer(..., keep_previous=True): the last call's history is looked up
+        where this frame's surfaces were under prev_inputs.  The first call, or one without a previous G-buffer, behaves
+        as reset=True.  motion=True also fills `self.motion` (rows, W, 2).  Returns the device RGBA8 buffer of the
+        accumulated colour; denoise(source="history") filters it."""
+        if source not in ("radiance", "accum"):
+            raise ValueError(f"source must be 'radiance' or 'accum', not {source!r}")
+        color = self.radiance if source == "radiance" else self.accum
+        if color is None:
+            raise RTError(f"temporal: no {source} plane (render with radiance=True / RT_FLAG_ACCUMULATE first)")
+        if self.normal_depth is None or self._gbuffer_inputs is None:
+            raise RTError("temporal: no G-buffer (call gbuffer() first)")
+        shape = (self.local_rows, self.width)
+        out = self._history_spare
+        if out is None:
+            out = torch.zeros(shape + (4,), dtype=torch.float32, device=self.device)
+        if self._temporal_pos is None:
+            self._temporal_pos = torch.zeros(self.width * self.local_rows, dtype=torch.int32, device=self.device)
+        if motion and self.motion is None:
+            self.motion = torch.zeros(shape + (2,), dtype=torch.float32, device=self.device)
+        reset = reset or self.history is None or self.prev_normal_depth is None or self.prev_inputs is None
+        a = abi.TemporalArgs()
+        a.color = color.data_ptr()
+        a.normal_depth, a.prim_id = self.normal_depth.data_ptr(), self.prim_id.data_ptr()
+        if not reset:
+            a.prev_history = self.history.data_ptr()
+            a.prev_normal_depth, a.prev_prim_id = self.prev_normal_depth.data_ptr(), self.prev_prim_id.data_ptr()
+            a.prev_inputs = self.prev_inputs
+        a.history = out.data_ptr()
+        a.motion = self.motion.data_ptr() if motion else None
+        a.pos = self._temporal_pos.data_ptr()
+        a.width, a.height, a.max_history = self.width, self.height, max_history
+        a.flags = (abi.RT_TEMPORAL_COLOR_IS_SUM if source == "accum" else 0) | (abi.RT_TEMPORAL_RESET if reset else 0)
+        a.depth_tol, a.normal_tol = depth_tol, normal_tol
+        a.tiling = self.tiling()
+        a.inputs = self._gbuffer_inputs
+        check(lib().rt_temporal(C.byref(a), C.c_void_p(self.stream())), "rt_temporal")
+        self.history, self._history_spare = out, self.history
+        return self._temporal_pos
 
     def image(self) -> np.ndarray:
         """Local framebuffer as (local_rows, W) uint32 RGBA8 (row 0 = bottom of the image)."""

@@ -182,8 +182,8 @@ const char* rt_version(void);
 
 /* Version of this C ABI (structure layouts, counter words, entry points); a caller built against an older header
  * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
- * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes. */
-#define RT_ABI_VERSION 7
+ * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal. */
+#define RT_ABI_VERSION 8
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -431,6 +431,70 @@ typedef struct rt_denoise_args {
 uint64_t rt_denoise_scratch_bytes(uint32_t width, uint32_t height, uint32_t iterations);
 /* The filter on `stream`, asynchronous; status codes and rt_last_error as rt_render. */
 int rt_denoise(const rt_denoise_args* args, rt_stream stream);
+
+/* ------------------------------------------------------------------------------------------------ */
+/* Reprojected temporal accumulation for moving cameras: the temporal half of the filter.  While the    */
+/* camera moves, RT_FLAG_ACCUMULATE restarts every frame; rt_temporal instead fetches the previous       */
+/* frame's accumulated colour where the surface seen at a pixel was in the previous frame, rejects it    */
+/* where that surface was hidden or is another one, and blends the new sample in.  It works on planes   */
+/* and two cameras: no scene handle.                                                                      */
+/* ------------------------------------------------------------------------------------------------ */
+enum rt_temporal_flags {
+    RT_TEMPORAL_COLOR_IS_SUM = 1u << 0, /* `color` is rt_render_args.accum: colour = rgb / w, 0 where w = 0 */
+    RT_TEMPORAL_RESET        = 1u << 1  /* no history is read (prev_* may be NULL): every pixel gets (colour, 1) */
+};
+
+/* Definition.  (O, fw, up, fov, near, far) come from an rt_input_struct; right = normalize(cross(up, fw)) as the
+ * kernels build it; k10 = (1 / fov) · 10.  Inputs are as rt_camera_inputs makes them: up unit and perpendicular to fw.
+ * Primed quantities belong to prev_inputs.  For a pixel p = (x, y) of the W × H frame:
+ *  0. Colour.  c = color.rgb, or rgb / w with RT_TEMPORAL_COLOR_IS_SUM (0 where w = 0).  If prim_id(p) < 0 or
+ *     RT_TEMPORAL_RESET is set: history(p) = (c, 1), motion(p) = (0, 0), done.
+ *  1. World point.  P = ro + t·rd with (ro, rd) the centre ray of rt_gbuffer under `inputs` (Kernel.cu:139-146 with
+ *     both jitter numbers 0.5) and t = normal_depth(p).w.
+ *  2. The inverse of that ray construction under prev_inputs.  q = P − O'; a = q·right', b = q·up',
+ *     c' = (q·fw') / (fw'·fw'); s = (c' − fov') / (k10' − fov'); den = near' + s·(far' − near').  No history if s <= 0
+ *     or den <= 0.  u = a / den, v = b / den; px = u·W + W/2 − 0.5, py = H/2 + 0.5 − v·W;
+ *     t_exp = |P − (O' + near'·(u·right' + v·up') + fov'·fw')|: the depth the previous G-buffer holds for this point
+ *     if it was visible.
+ *  3. Snap.  A coordinate within 1/256 of an integer becomes that integer: a resting camera reads exactly its own
+ *     pixel (one tap, weight 1), and the accumulation is the running mean with no resampling blur.
+ *  4. Bilinear fetch.  x0 = floor(px), fx = px − x0, likewise y.  The four taps (x0 + i, y0 + j) have weight w_ij =
+ *     (fx or 1 − fx)·(fy or 1 − fy).  A tap counts if w_ij > 0, it lies inside the frame, prev_prim_id == prim_id(p),
+ *     prev_history.w > 0, |prev_t − t_exp| <= depth_tol · max(t_exp, 1e-3) and n_p · n'_tap >= 1 − normal_tol.
+ *     S = Σ w over the counting taps; history exists if S >= 1/100, then h = Σ w·rgb / S and L = Σ w·len / S (with both
+ *     coordinates snapped that is the single tap as it is).
+ *  5. Blend.  N = min(L + 1, max_history), alpha = 1 / N, history(p) = (h + alpha·(c − h), N); with no history
+ *     history(p) = (c, 1).  motion(p) = (px − x, py − y) after the snap whenever step 2 succeeded, else (0, 0).
+ *     pos(p) is the stored rgb through the render kernels' epilogue (255·sqrtf, clamp, truncate, alpha 255).
+ * Arithmetic is binary32 without contraction, 1 / N correctly rounded: a resting camera gives h + (1/N)·(c − h) bit for
+ * bit.  One launch, no atomics, every pixel written by one lane: two calls on the same inputs give the same bits.
+ * Buffers are height × width elements, row 0 at the bottom.  The gather reads pixels other workgroups write, so an
+ * output overlapping a prev_* plane is rejected (RT_ERR_INVALID_ARGUMENT; history aliasing prev_history, fully or
+ * partly, with a message naming the alias): the caller ping-pongs two history planes and two G-buffer sets.  The taps
+ * cross band boundaries: a tiling with num_ranks > 1 is rejected.  The result feeds rt_denoise as `color` with plain
+ * flags (the filter reads rgb and ignores w); history.w tells a viewer when the filter can be skipped.
+ * Limits: what a mirror or a glass sphere shows is reprojected with the sphere's surface, so reflections lag behind a
+ * moving camera; a scene edit changes what primitive ids mean and needs RT_TEMPORAL_RESET. */
+typedef struct rt_temporal_args {
+    const float*   color;             /* float4: this frame's radiance (or accum with COLOR_IS_SUM) */
+    const float*   normal_depth;      /* this frame's rt_gbuffer planes */
+    const int32_t* prim_id;
+    const float*   prev_history;      /* float4: rgb = accumulated colour, w = history length, from the last call */
+    const float*   prev_normal_depth; /* the previous frame's rt_gbuffer planes */
+    const int32_t* prev_prim_id;
+    float*    history;                /* out, float4: rgb, w = history length N (>= 1) */
+    float*    motion;                 /* optional out, float2: (px - x, py - y), 0 where there is none */
+    uint32_t* pos;                    /* optional out: RGBA8 of history.rgb through the render kernels' epilogue */
+    uint32_t width, height, flags;    /* rt_temporal_flags */
+    uint32_t max_history;             /* 1..4096; the blend weight never falls below 1 / max_history */
+    float depth_tol, normal_tol;      /* > 0; start from 0.05 and 0.2 */
+    uint32_t reserved[2];             /* must be 0 */
+    rt_tiling tiling;                 /* whole frame only, as rt_denoise */
+    rt_input_struct inputs;           /* this frame's camera */
+    rt_input_struct prev_inputs;      /* the previous frame's camera */
+} rt_temporal_args;                   /* 264 B */
+/* The pass on `stream`, asynchronous; status codes and rt_last_error as rt_render. */
+int rt_temporal(const rt_temporal_args* args, rt_stream stream);
 
 /* Tuning/benchmark knob (per thread): the kernel rt_render launches.  -1 = automatic: 3 from 64 spp; below,
  * the faster of 3 and 4 as timed on the first frames of each (device, stream, scene, frame shape, spp, depth,

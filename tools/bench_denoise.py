@@ -7,6 +7,12 @@ of the scripted camera orbit.  Prints one JSON line: ms, the compulsory bytes of
 colour plane read and one written and the normal/depth plane read, 16 B per pixel each; the first iteration also reads
 prim_id, 4 B, and the albedo, 16 B; the last reads the albedo and writes the RGBA8 framebuffer, 4 B; the G-buffer pass
 writes its 36 B per pixel) and the GB/s they amount to, and each pass's ratio to the render time of the same run.
+
+`temporal` times rt_temporal in the same loop (colour from the accumulator, motion and RGBA8 outputs on, defaults
+otherwise).  The camera really moves between frames (6 degrees of the orbit) and the G-buffer keeps the previous frame's
+planes, so every call reprojects.  Its compulsory bytes per pixel: 36 of the current planes read, 36 of the previous
+planes gathered (the four taps of neighbouring pixels overlap: about one plane set of unique bytes), 16 of history, 8 of
+motion and 4 of RGBA8 written: 100.  `history_share` is the share of pixels that found history in the last frame.
 """
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -47,14 +53,15 @@ def timed(fn) -> float:
     return e0.elapsed_time(e1)
 
 
-times = {"render": [], "gbuffer": [], **{f"denoise_n{n}": [] for n in ITER}}
+times = {"render": [], "gbuffer": [], "temporal": [], **{f"denoise_n{n}": [] for n in ITER}}
 total = args.warmup + args.frames
 for f in range(total):
     pos, fwd = scenes.moving_camera(f % 60, 60)
     inp = scenes.camera_inputs(pos, fwd, cfg.fov)
     r.reset_accumulation()
     t = {"render": timed(lambda: r.render(ds, cfg.spp, cfg.depth, inp, flags=abi.RT_FLAG_ACCUMULATE, count=False)),
-         "gbuffer": timed(lambda: r.gbuffer(ds, inp))}
+         "gbuffer": timed(lambda: r.gbuffer(ds, inp, keep_previous=True))}
+    t["temporal"] = timed(lambda: r.temporal(source="accum", motion=True))
     for n in ITER:
         t[f"denoise_n{n}"] = timed(lambda: r.denoise_async(iterations=n, source="accum"))
     if f >= args.warmup:
@@ -67,6 +74,10 @@ out = {"config": "c5", "workload": f"{cfg.width}x{cfg.height}, {cfg.spp} spp, de
 gb = npix * 36
 out["gbuffer"] = {"ms": round(ms["gbuffer"], 4), "bytes": gb, "GB_per_s": round(gb / ms["gbuffer"] / 1e6, 1),
                   "ratio_to_render": round(ms["gbuffer"] / ms["render"], 3)}
+tb = npix * 100
+out["temporal"] = {"ms": round(ms["temporal"], 4), "bytes": tb, "GB_per_s": round(tb / ms["temporal"] / 1e6, 1),
+                   "ratio_to_render": round(ms["temporal"] / ms["render"], 3),
+                   "history_share": round(float((r.history[..., 3] > 1.0).float().mean().item()), 3)}
 for n in ITER:
     m, b = ms[f"denoise_n{n}"], denoise_bytes(n)
     out[f"denoise_n{n}"] = {"ms": round(m, 4), "bytes": b, "GB_per_s": round(b / m / 1e6, 1),

@@ -50,6 +50,9 @@ EXPORTED = [
     "rt_denoise",
     "rt_denoise_scratch_bytes",
     "rt_temporal",
+    "rt_temporal_dynamic",
+    "rt_scene_motion",
+    "rt_scene_edit",
     "rt_last_kernel_ms",
     "rt_last_variant",
     "rt_last_launch_host_ms",
@@ -107,6 +110,9 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
     lib.rt_denoise_scratch_bytes.restype = C.c_uint64
     lib.rt_temporal.argtypes = [P(abi.TemporalArgs), vp]
+    lib.rt_temporal_dynamic.argtypes = [P(abi.TemporalArgs), vp, C.c_uint32, vp]
+    lib.rt_scene_motion.argtypes = [P(abi.HittableDesc), P(abi.HittableDesc), C.c_uint32, P(C.c_float)]
+    lib.rt_scene_edit.argtypes = [vp, P(abi.HittableDesc), C.c_uint32, P(vp)]
     lib.rt_last_kernel_ms.restype = C.c_float
     lib.rt_last_variant.restype = C.c_int
     lib.rt_last_launch_host_ms.restype = C.c_float

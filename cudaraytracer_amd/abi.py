@@ -26,6 +26,10 @@ RT_DENOISE_DEMODULATE = 1 << 0
 RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
 RT_TEMPORAL_RESET = 1 << 1
+ABI_VERSION = 9  # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit
+# entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
+MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
+MOTION_IDENTITY = (0.0, 0.0, 0.0, 1.0)
 COUNTERS_WORDS = 24  # RT_COUNTERS_WORDS: the counters buffer with RT_FLAG_COUNT_TESTS
 PHILOX_MAX_SPP = 16384  # RT_PHILOX_MAX_SPP
 # rt_set_tuning keys (rt_tuning_key in include/rt_hip.h)

@@ -148,6 +148,27 @@ fail:
     return rc;
 }
 
+// What rt_scene_edit rebuilds a scene from: the materials, the images' sizes (and whether each had data: the texels
+// themselves stay on the device) and the hittable count that gives rt_gbuffer's prim_id values their meaning.
+// A failed host allocation frees the new scene, clears the handle and goes on to the caller's guard.
+static void keep_description(rt_scene** scene, const rt_scene_desc& d, int texel_bytes) {
+    static const uint8_t kHasData = 0;  // stands for "this image has texels"; never read (build_host_scene, with_texels = false)
+    rt_scene* s = *scene;
+    try {
+        s->materials.assign(d.materials, d.materials + d.num_materials);
+        s->images.assign(d.images, d.images + d.num_images);
+    } catch (...) {
+        rt_scene_destroy(s);
+        *scene = nullptr;
+        throw;
+    }
+    for (rt_image_desc& im : s->images)
+        if (im.data) im.data = &kHasData;
+    s->num_hittables = d.num_hittables;
+    s->texel_bytes = texel_bytes;
+    s->described = true;
+}
+
 // ------------------------------------------------------------------------------------------------
 // Reference pointer-graph flattener.  Walks BVHNode::left/right (Hittable.cuh:296-301) from `world`,
 // collects each distinct leaf hittable once (span-1 leaves reference one object twice, Hittable.cuh:
@@ -402,7 +423,11 @@ int rt_scene_create(const rt_scene_desc* desc, rt_scene** out_scene) {
         std::string err;
         int rc = build_host_scene(desc, &h, &err);
         if (rc) { set_error("rt_scene_create: " + err); return rc; }
-        return create_device_scene(h, out_scene);
+        rc = create_device_scene(h, out_scene);
+        if (rc) return rc;
+        keep_description(out_scene, *desc, g_texel_bytes == 4 ? 4 : 3);
+        (*out_scene)->texel_block_bytes = h.texels.size();
+        return RT_OK;
     });
 }
 
@@ -450,6 +475,7 @@ int rt_scene_update_materials(rt_scene* scene, const rt_material_desc* materials
         scene->dev.has_image_textures = img;
         scene->dev.has_textures = tex;
         scene->host.mats = packed;
+        if (scene->described) scene->materials.assign(materials, materials + num_materials);  // what rt_scene_edit rebuilds from
         return RT_OK;
     });
 }
@@ -535,10 +561,11 @@ static TemporalCamera temporal_camera(const rt_input_struct& in) {
     return c;
 }
 
-int rt_temporal(const rt_temporal_args* a, rt_stream stream) {
-    // (every check runs before the first device call)
-    const auto bad = [](const char* msg) {
-        set_error(std::string("rt_temporal: ") + msg);
+// The checks of rt_temporal (and, under its own name, of rt_temporal_dynamic) and the launch parameters: RT_OK with *P
+// filled and *pixels = width · height, or RT_ERR_INVALID_ARGUMENT with the error set.  No device call.
+static int temporal_params(const char* who, const rt_temporal_args* a, TemporalParams* out, uint64_t* pixels) {
+    const auto bad = [who](const char* msg) {
+        set_error(std::string(who) + ": " + msg);
         return (int)RT_ERR_INVALID_ARGUMENT;
     };
     if (!a) return bad("NULL args");
@@ -566,8 +593,9 @@ int rt_temporal(const rt_temporal_args* a, rt_stream stream) {
                     return bad(o == 0 && i == 0 ? "history must not alias prev_history (ping-pong two planes)"
                                                 : "an output overlaps a prev_* plane");
     }
-    if (n == 0) return RT_OK;
-    TemporalParams P{};
+    *pixels = n;
+    TemporalParams& P = *out;
+    P = TemporalParams{};
     P.color = a->color;
     P.normal_depth = a->normal_depth;
     P.prim_id = a->prim_id;
@@ -588,7 +616,110 @@ int rt_temporal(const rt_temporal_args* a, rt_stream stream) {
     P.half_h = (float)a->height / 2.0f;
     P.cur = temporal_camera(a->inputs);
     P.prev = reset ? P.cur : temporal_camera(a->prev_inputs);  // (prev_inputs is not read with RT_TEMPORAL_RESET)
+    return RT_OK;
+}
+
+int rt_temporal(const rt_temporal_args* a, rt_stream stream) {
+    // (every check runs before the first device call)
+    TemporalParams P;
+    uint64_t n = 0;
+    const int rc = temporal_params("rt_temporal", a, &P, &n);
+    if (rc || n == 0) return rc;
     return launch_temporal(P, stream);
+}
+
+int rt_temporal_dynamic(const rt_temporal_args* a, const float* prim_motion, uint32_t num_prims, rt_stream stream) {
+    TemporalParams P;
+    uint64_t n = 0;
+    const int rc = temporal_params("rt_temporal_dynamic", a, &P, &n);
+    if (rc) return rc;
+    const auto bad = [](const char* msg) {
+        set_error(std::string("rt_temporal_dynamic: ") + msg);
+        return (int)RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!(a->flags & RT_TEMPORAL_RESET)) {  // (with RT_TEMPORAL_RESET the table is never read)
+        if (!prim_motion) return bad("NULL prim_motion without RT_TEMPORAL_RESET");
+        if ((uintptr_t)prim_motion % 16u) return bad("prim_motion must be 16-byte aligned (float4 entries)");
+        const void* outs[3] = {a->history, a->motion, a->pos};
+        const uint64_t out_bytes[3] = {n * 16u, n * 8u, n * 4u};
+        for (int o = 0; o < 3; o++)
+            if (overlaps(outs[o], out_bytes[o], prim_motion, (uint64_t)num_prims * 16u))
+                return bad("an output overlaps the prim_motion table");
+    }
+    if (n == 0) return RT_OK;
+    return launch_temporal_dynamic(P, prim_motion, num_prims, stream);
+}
+
+int rt_scene_motion(const rt_hittable_desc* prev, const rt_hittable_desc* cur, uint32_t num_hittables, float* table) {
+    if (num_hittables && (!prev || !cur || !table)) {
+        set_error("rt_scene_motion: NULL argument with num_hittables > 0");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    // (this file is compiled -ffp-contract=off: every operation below is one binary32 rounding)
+    for (uint32_t i = 0; i < num_hittables; i++) {
+        const rt_hittable_desc& p = prev[i];
+        const rt_hittable_desc& c = cur[i];
+        float* m = table + (size_t)i * 4;
+        m[0] = m[1] = m[2] = m[3] = 0.0f;  // no history
+        if (!p.is_active || !c.is_active || p.type != c.type) continue;
+        const bool sphere = c.type == RT_SPHERE;
+        if (!sphere && c.type != RT_XYRECT && c.type != RT_XZRECT && c.type != RT_YZRECT) continue;
+        if (sphere ? !(p.radius > 0.0f && c.radius > 0.0f) : !(p.width == c.width && p.height == c.height)) continue;
+        const auto same_bits = [](const float a, const float b) { return std::memcmp(&a, &b, sizeof(float)) == 0; };
+        const bool same_size = sphere ? same_bits(p.radius, c.radius)
+                                      : same_bits(p.width, c.width) && same_bits(p.height, c.height);
+        if (same_size && std::memcmp(p.center, c.center, sizeof(p.center)) == 0) {
+            m[3] = 1.0f;  // at rest: exactly (0, 0, 0, 1), which the kernel passes through without arithmetic
+            continue;
+        }
+        const float s = sphere ? p.radius / c.radius : 1.0f;
+        for (int k = 0; k < 3; k++) {
+            const float scaled = s * c.center[k];
+            m[k] = p.center[k] - scaled;
+        }
+        m[3] = s;
+    }
+    return RT_OK;
+}
+
+int rt_scene_edit(const rt_scene* base, const rt_hittable_desc* hittables, uint32_t num_hittables, rt_scene** out) {
+    if (!out) { set_error("rt_scene_edit: out is NULL"); return RT_ERR_INVALID_ARGUMENT; }
+    *out = nullptr;
+    if (!base || (!hittables && num_hittables)) { set_error("rt_scene_edit: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
+    if (!base->described) {
+        set_error("rt_scene_edit: the base scene keeps no description");
+        return RT_ERR_UNSUPPORTED;
+    }
+    if (num_hittables != base->num_hittables) {
+        set_error("rt_scene_edit: hittable count " + std::to_string(num_hittables) + " differs from the base scene's " +
+                  std::to_string(base->num_hittables) + " (primitive ids would change their meaning)");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    return guarded("rt_scene_edit", [&]() -> int {
+        rt_scene_desc d;
+        d.hittables = hittables;
+        d.num_hittables = num_hittables;
+        d.materials = base->materials.data();
+        d.num_materials = (uint32_t)base->materials.size();
+        d.images = base->images.data();
+        d.num_images = (uint32_t)base->images.size();
+        HostScene h;
+        std::string err;
+        // the image table must describe the block `base` uploaded: its texel layout, not this thread's current one
+        struct Layout {
+            const int saved = g_texel_bytes;
+            ~Layout() { g_texel_bytes = saved; }
+        } layout;
+        g_texel_bytes = base->texel_bytes;
+        const int rc = build_host_scene(&d, &h, &err, /*with_texels=*/false);
+        if (rc) { set_error("rt_scene_edit: " + err); return rc; }
+        const int r = create_device_scene(h, out, base->texel_block);
+        if (r) return r;
+        keep_description(out, d, base->texel_bytes);
+        (*out)->texel_block_bytes = base->texel_block_bytes;
+        (*out)->dev.device_bytes += base->texel_block_bytes;  // (shared with `base`, counted in both)
+        return RT_OK;
+    });
 }
 
 int rt_scene_destroy(rt_scene* scene) {

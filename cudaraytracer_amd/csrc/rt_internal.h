@@ -151,6 +151,8 @@ struct TemporalParams {
 };
 // One launch on `stream` (a hipStream_t); RT_OK or RT_ERR_LAUNCH with the error set.
 int launch_temporal(const TemporalParams& P, void* stream);
+// rt_temporal_dynamic's launch: prim_motion = num_prims float4 entries on the device (may be NULL with RT_TEMPORAL_RESET)
+int launch_temporal_dynamic(const TemporalParams& P, const float* prim_motion, uint32_t num_prims, void* stream);
 
 inline float bits_to_float(uint32_t u) {
     float f;

@@ -51,4 +51,12 @@ struct rt_scene {
     rt::HostScene host;  // packed tables (texels dropped after the upload)
     rt::DeviceScene dev;
     std::shared_ptr<void> texel_block;  // device texels, shared by scenes rebuilt from the same images
+    // The part of the description rt_scene_edit needs (rt_scene_create keeps it; LaunchKernel's cached scenes do not:
+    // described = false).  images[i].data is NULL or a placeholder for "has texels": the host texels are not kept.
+    bool described = false;
+    uint32_t num_hittables = 0;  // entries of the caller's hittable list, inactive ones counted
+    std::vector<rt_material_desc> materials;  // as the last rt_scene_update_materials left them
+    std::vector<rt_image_desc> images;
+    int texel_bytes = 3;            // device bytes per texel of texel_block (RT_TUNE_TEXEL_LAYOUT when it was uploaded)
+    uint64_t texel_block_bytes = 0; // size of texel_block
 };

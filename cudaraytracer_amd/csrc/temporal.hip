@@ -17,6 +17,9 @@
 // operations and their order are those of the numpy restatement (tests/test_temporal_host.py temporal_reference in
 // float32).  A resting camera snaps to its own pixel: one tap of weight 1, so the result is h + (1/N)·(c − h) bit for
 // bit.
+// rt_temporal_dynamic is a second kernel over the same body: between the world point and the camera
+// inverse it moves the point by its hittable's entry of a per-hittable motion table (rt_scene_motion), so history
+// survives object edits; tests/test_dynamic_host.py temporal_dynamic_reference restates it.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -47,7 +50,12 @@ __device__ __forceinline__ v3 ray_start(const TemporalCamera& C, const float u, 
     return (C.near_plane * dist + ld3(C.origin)) + ld3(C.fov_fwd);
 }
 
-__global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_kernel(const TemporalParams P) {
+// The pass's body.  DYNAMIC = false is rt_temporal; DYNAMIC = true is rt_temporal_dynamic: step 1a, the
+// hittable's motion entry table[id] = (o.xyz, s), moves the world point to where that surface point was in the previous
+// scene before the camera inverse.  The static build holds none of it (if constexpr): temporal_kernel keeps the 63
+// VGPRs and 905 instructions it had before the second kernel existed.
+template <bool DYNAMIC>
+__device__ __forceinline__ void temporal_body(const TemporalParams& P, const float4* table, const uint32_t num_prims) {
     const uint32_t x = blockIdx.x * kTpTileW + threadIdx.x, y = blockIdx.y * kTpTileH + threadIdx.y;
     if (x >= P.width || y >= P.height) return;
     const int W = (int)P.width, H = (int)P.height;
@@ -61,7 +69,14 @@ __global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_kernel(const Tem
     float4 out = make_float4(c.x, c.y, c.z, 1.0f);
     float2 mv = make_float2(0.0f, 0.0f);
     const int id = P.prim_id[pix];
-    if (id >= 0 && !(P.flags & RT_TEMPORAL_RESET)) {
+    // 1a. the hittable's motion entry: one 16-byte load per lane (neighbouring lanes mostly share the entry: the table
+    // is a few cache lines); an id beyond the table or s == 0 means no history
+    float4 m = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    if constexpr (DYNAMIC) {
+        if (id >= 0 && (uint32_t)id < num_prims && !(P.flags & RT_TEMPORAL_RESET)) m = table[id];
+        else m.w = 0.0f;
+    }
+    if (id >= 0 && !(P.flags & RT_TEMPORAL_RESET) && m.w != 0.0f) {
         const float4 nd = ((const float4*)P.normal_depth)[pix];
         // 1. the world point on rt_gbuffer's centre ray
         const float u = (((float)(int)x - P.half_w) + 0.5f) / P.width_f;
@@ -72,7 +87,11 @@ __global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_kernel(const Tem
         const v3 d = second - ro;
         const float inv = 1.0f / sqrtf(dot3(d, d));
         const v3 rd = inv * d;
-        const v3 Pw = ro + nd.w * rd;
+        v3 Pw = ro + nd.w * rd;
+        if constexpr (DYNAMIC) {
+            // (0, 0, 0, 1) leaves the point as it is; else one multiply, then one add per component
+            if (!(m.x == 0.0f && m.y == 0.0f && m.z == 0.0f && m.w == 1.0f)) Pw = m.w * Pw + v3{m.x, m.y, m.z};
+        }
         // 2. the inverse of the ray construction under the previous camera
         const TemporalCamera& Q = P.prev;
         const v3 q = Pw - ld3(Q.origin);
@@ -150,6 +169,17 @@ __global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_kernel(const Tem
     if (P.pos) P.pos[pix] = rgb_to_int(255.0f * sqrtf(out.x), 255.0f * sqrtf(out.y), 255.0f * sqrtf(out.z));
 }
 
+__global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_kernel(const TemporalParams P) {
+    temporal_body<false>(P, nullptr, 0u);
+}
+
+// rt_temporal_dynamic: the same launch shape; `table` holds num_prims float4 entries (never read with RT_TEMPORAL_RESET)
+__global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_dynamic_kernel(const TemporalParams P,
+                                                                               const float4* __restrict__ table,
+                                                                               const uint32_t num_prims) {
+    temporal_body<true>(P, table, num_prims);
+}
+
 }  // namespace dev
 
 int launch_temporal(const TemporalParams& P, void* stream) {
@@ -160,6 +190,20 @@ int launch_temporal(const TemporalParams& P, void* stream) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error(std::string("rt_temporal: kernel launch: ") + hipGetErrorString(e));
+        return RT_ERR_LAUNCH;
+    }
+    return RT_OK;
+}
+
+int launch_temporal_dynamic(const TemporalParams& P, const float* prim_motion, uint32_t num_prims, void* stream) {
+    const dim3 block(dev::kTpTileW, dev::kTpTileH);
+    const dim3 grid((P.width + dev::kTpTileW - 1) / dev::kTpTileW, (P.height + dev::kTpTileH - 1) / dev::kTpTileH);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(dev::temporal_dynamic_kernel, grid, block, 0, (hipStream_t)stream, P, (const float4*)prim_motion,
+                       num_prims);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string("rt_temporal_dynamic: kernel launch: ") + hipGetErrorString(e));
         return RT_ERR_LAUNCH;
     }
     return RT_OK;

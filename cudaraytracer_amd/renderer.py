@@ -40,6 +40,21 @@ class DeviceScene:
         check(lib().rt_scene_update_materials(self.handle, C.cast(materials, C.POINTER(abi.MaterialDesc)),
                                               len(materials)), "rt_scene_update_materials")
 
+    def edited(self, hittables) -> "DeviceScene":
+        """A new device scene with this one's materials and images and the given hittable list (rt_scene_edit): the
+        same count and order, so primitive ids keep their meaning; the uploaded texels are shared, not copied.  Both
+        scenes stay valid and are closed independently."""
+        from .scenes import _hittable_array
+        new = DeviceScene.__new__(DeviceScene)
+        new.handle = C.c_void_p()
+        arr = _hittable_array(hittables)
+        new.scene = None
+        if self.scene is not None:
+            copy = (abi.HittableDesc * len(arr)).from_buffer_copy(arr)
+            new.scene = Scene(copy, self.scene.materials, self.scene.images)
+        check(lib().rt_scene_edit(self.handle, arr, len(arr), C.byref(new.handle)), "rt_scene_edit")
+        return new
+
     def close(self) -> None:
         if self.handle:
             lib().rt_scene_destroy(self.handle)
@@ -110,6 +125,7 @@ class Renderer:
         self._history_spare = None   # ... the plane the next call writes (the two ping-pong)
         self.motion = None           # temporal(motion=True): (local_rows × W × 2) float32
         self._temporal_pos = None
+        self._prim_motion = None     # temporal(prim_motion=...): the device table of the last call
 
     def tiling(self) -> abi.Tiling:
         return abi.Tiling(self.band_rows, self.num_ranks, self.rank, self.local_rows)
@@ -239,13 +255,16 @@ class Renderer:
         return self._denoise_pos
 
     def temporal(self, max_history: int = 32, depth_tol: float = 0.05, normal_tol: float = 0.2,
-                 source: str = "radiance", reset: bool = False, motion: bool = False) -> torch.Tensor:
+                 source: str = "radiance", reset: bool = False, motion: bool = False, prim_motion=None) -> torch.Tensor:
         """Reprojected temporal accumulation (rt_temporal) of the last frame's `radiance` or `accum` plane into
         `self.history` (rows, W, 4: rgb, history length), asynchronous on torch's current stream; whole frames only.
         Call once per frame after render() and gbuffer(..., keep_previous=True): the last call's history is looked up
         where this frame's surfaces were under prev_inputs.  The first call, or one without a previous G-buffer, behaves
         as reset=True.  motion=True also fills `self.motion` (rows, W, 2).  Returns the device RGBA8 buffer of the
-        accumulated colour; denoise(source="history") filters it."""
+        accumulated colour; denoise(source="history") filters it.
+        prim_motion: the (n, 4) float32 per-hittable motion table of an object edit between the two frames
+        (scenes.scene_motion; a torch tensor on this device or a numpy array, which is uploaded): the pass then runs as
+        rt_temporal_dynamic and history follows the moved hittables.  None keeps the rt_temporal call."""
         if source not in ("radiance", "accum"):
             raise ValueError(f"source must be 'radiance' or 'accum', not {source!r}")
         color = self.radiance if source == "radiance" else self.accum
@@ -277,7 +296,19 @@ class Renderer:
         a.depth_tol, a.normal_tol = depth_tol, normal_tol
         a.tiling = self.tiling()
         a.inputs = self._gbuffer_inputs
-        check(lib().rt_temporal(C.byref(a), C.c_void_p(self.stream())), "rt_temporal")
+        if prim_motion is None:
+            check(lib().rt_temporal(C.byref(a), C.c_void_p(self.stream())), "rt_temporal")
+        else:
+            table = prim_motion
+            if not isinstance(table, torch.Tensor):
+                table = torch.from_numpy(np.array(table, dtype=np.float32))
+            if table.device != self.device or table.dtype != torch.float32 or not table.is_contiguous():
+                table = table.to(device=self.device, dtype=torch.float32).contiguous()
+            if table.numel() % 4:
+                raise ValueError("temporal: prim_motion holds four floats per hittable")
+            self._prim_motion = table  # (kept until the next call: the launch is asynchronous)
+            check(lib().rt_temporal_dynamic(C.byref(a), C.c_void_p(table.data_ptr() if table.numel() else None),
+                                            table.numel() // 4, C.c_void_p(self.stream())), "rt_temporal_dynamic")
         self.history, self._history_spare = out, self.history
         return self._temporal_pos
 

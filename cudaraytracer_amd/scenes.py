@@ -68,6 +68,28 @@ class Scene:
         return cls(h, m, list(images or []))
 
 
+def _hittable_array(hittables) -> C.Array:
+    """A Scene, a ctypes array of HittableDesc or a sequence of them as one contiguous ctypes array."""
+    hittables = getattr(hittables, "hittables", hittables)
+    if isinstance(hittables, C.Array) and hittables._type_ is abi.HittableDesc:
+        return hittables
+    return (abi.HittableDesc * len(hittables))(*hittables)
+
+
+def scene_motion(prev_scene, scene) -> np.ndarray:
+    """The per-hittable motion table of an object edit (rt_scene_motion, host only): (n, 4) float32 rows (o.x, o.y, o.z, s)
+    mapping a surface point of hittable i in `scene` to the same point in `prev_scene`, s·P + o; (0, 0, 0, 0) = no
+    history, (0, 0, 0, 1) = at rest.  Both arguments are Scenes or hittable arrays of the same length and order.  A
+    hittable whose material changed needs its row zeroed by the caller.  Renderer.temporal(prim_motion=...) takes the
+    result."""
+    prev, cur = _hittable_array(prev_scene), _hittable_array(scene)
+    if len(prev) != len(cur):
+        raise ValueError(f"scene_motion: {len(prev)} hittables before the edit, {len(cur)} after")
+    table = np.zeros((len(cur), 4), dtype=np.float32)
+    check(lib().rt_scene_motion(prev, cur, len(cur), table.ctypes.data_as(C.POINTER(C.c_float))), "rt_scene_motion")
+    return table
+
+
 TEXTURE_EARTH, TEXTURE_MOON, TEXTURE_SUN = 0, 1, 2
 DEFAULT_TEXTURE_SIZE = (1024, 512)  # parity fixtures; BASELINE config 5 uses the reference's 8192x4096
 

@@ -182,8 +182,9 @@ const char* rt_version(void);
 
 /* Version of this C ABI (structure layouts, counter words, entry points); a caller built against an older header
  * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
- * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal. */
-#define RT_ABI_VERSION 8
+ * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal.  9: rt_scene_motion, rt_temporal_dynamic,
+ * rt_scene_edit. */
+#define RT_ABI_VERSION 9
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -201,6 +202,31 @@ int rt_scene_from_reference_graph(const void* world, rt_scene** out_scene);
 /* Replace materials/textures in place (no BVH rebuild), like the viewer's material edits
  * (CudaLayer.cpp:719-872).  num_materials must equal the scene's material count. */
 int rt_scene_update_materials(rt_scene* scene, const rt_material_desc* materials, uint32_t num_materials);
+
+/* A geometry edit without the image upload: a new scene from `base`'s materials (as the last
+ * rt_scene_update_materials left them) and images and the given hittable list, like the viewer's object edits
+ * (CudaLayer.cpp:470-900: a centre dragged, a radius changed, isActive toggled).  Validation, the BVH, the reference
+ * tree and the flat tables are those rt_scene_create builds from the full description (with this thread's
+ * RT_TUNE_LEAF_MAX / RT_TUNE_SAH_TRAVERSAL); the image table keeps the texel layout `base` was created with, and the
+ * new scene references `base`'s device texel block instead of copying or uploading it again (C5: 3 x 100 MB).
+ * num_hittables must equal the count `base` was described with (RT_ERR_INVALID_ARGUMENT), so rt_gbuffer's prim_id
+ * values keep their meaning across the edit.  `base` stays valid; the two handles are destroyed independently, in
+ * either order (the texel block is freed with the last of them).  The current device must be the one `base` lives on.
+ * `base` may itself come from rt_scene_edit, rt_scene_create or rt_scene_from_reference_graph. */
+int rt_scene_edit(const rt_scene* base, const rt_hittable_desc* hittables, uint32_t num_hittables, rt_scene** out);
+
+/* Host only, no device: the per-hittable motion table rt_temporal_dynamic takes, from the hittable lists before and
+ * after an edit (same length, same order).  table[4i .. 4i+3] = (o.x, o.y, o.z, s) maps a surface point P of hittable i
+ * now to the same surface point in the previous scene, s·P + o, evaluated in binary32 (one rounding per operation):
+ *   - (0, 0, 0, 0) = no history: either description inactive, the types differ, a sphere with radius <= 0 in either
+ *     description, or a rectangle whose width or height differs;
+ *   - else a hittable whose centre and size (sphere: radius; rectangle: width, height) are bitwise unchanged gets
+ *     exactly (0, 0, 0, 1);
+ *   - else a sphere gets s = r_prev / r_cur, o = c_prev − s·c_cur, a rectangle s = 1, o = c_prev − c_cur.
+ * Materials are not compared: a changed material on a hittable invalidates its accumulated colour, and the caller
+ * zeroes that entry (all four floats) before the upload.  NULL pointers with num_hittables > 0 are rejected
+ * (RT_ERR_INVALID_ARGUMENT). */
+int rt_scene_motion(const rt_hittable_desc* prev, const rt_hittable_desc* cur, uint32_t num_hittables, float* table);
 
 int rt_scene_destroy(rt_scene* scene);
 
@@ -474,7 +500,8 @@ enum rt_temporal_flags {
  * cross band boundaries: a tiling with num_ranks > 1 is rejected.  The result feeds rt_denoise as `color` with plain
  * flags (the filter reads rgb and ignores w); history.w tells a viewer when the filter can be skipped.
  * Limits: what a mirror or a glass sphere shows is reprojected with the sphere's surface, so reflections lag behind a
- * moving camera; a scene edit changes what primitive ids mean and needs RT_TEMPORAL_RESET. */
+ * moving camera.  rt_temporal assumes the hittables rest between the two frames; across an object edit call
+ * rt_temporal_dynamic below. */
 typedef struct rt_temporal_args {
     const float*   color;             /* float4: this frame's radiance (or accum with COLOR_IS_SUM) */
     const float*   normal_depth;      /* this frame's rt_gbuffer planes */
@@ -495,6 +522,26 @@ typedef struct rt_temporal_args {
 } rt_temporal_args;                   /* 264 B */
 /* The pass on `stream`, asynchronous; status codes and rt_last_error as rt_render. */
 int rt_temporal(const rt_temporal_args* args, rt_stream stream);
+
+/* rt_temporal across object edits: hittables moved, resized or switched off between the two frames (rt_scene_edit), with
+ * or without camera motion.  prim_motion is a device table of num_prims float4 entries (o.x, o.y, o.z, s) as
+ * rt_scene_motion computes them, indexed by prim_id: both frames' ids must index the same hittable list.  The definition
+ * is rt_temporal's with one step between 1 and 2.  Let m = prim_motion[prim_id(p)]:
+ *  1a. Object motion.  If prim_id(p) >= num_prims or m.s == 0 the pixel has no history: history(p) = (c, 1),
+ *      motion(p) = (0, 0), done.  If m is exactly (0, 0, 0, 1), P~ = P (no arithmetic); otherwise P~ = s·P + o per
+ *      component: one multiply, then one add, no contraction.  P~ is where this surface point was in the previous scene.
+ * Steps 2-5 run on P~ (q = P~ − O', t_exp from P~), the prev_prim_id == prim_id test included; the normal test compares
+ * the two frames' normals as they are (a sphere's normal at a surface point does not change under translation and
+ * uniform scaling).  motion(p) therefore holds camera plus object motion.  With an all-identity table of at least
+ * max(prim_id) + 1 entries the call gives rt_temporal's bits.
+ * Arguments: rt_temporal's checks apply.  prim_motion must be non-NULL unless RT_TEMPORAL_RESET is set; the table is
+ * then never read and the call is rt_temporal with the flag.  The table (16·num_prims bytes) must not overlap an output
+ * (RT_ERR_INVALID_ARGUMENT, with a message naming prim_motion).  One launch, one 16-byte table load per hit pixel, no
+ * atomics: two calls on the same inputs give the same bits.
+ * Limits: as rt_temporal, reflections lag behind a moving camera; shadows and reflections of a moved object on other
+ * surfaces lag by up to max_history frames (those surfaces keep their history: nothing they are tested by changed); a
+ * hittable whose material changed needs its entry zeroed by the caller. */
+int rt_temporal_dynamic(const rt_temporal_args* args, const float* prim_motion, uint32_t num_prims, rt_stream stream);
 
 /* Tuning/benchmark knob (per thread): the kernel rt_render launches.  -1 = automatic: 3 from 64 spp; below,
  * the faster of 3 and 4 as timed on the first frames of each (device, stream, scene, frame shape, spp, depth,

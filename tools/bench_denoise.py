@@ -13,6 +13,12 @@ otherwise).  The camera really moves between frames (6 degrees of the orbit) and
 planes, so every call reprojects.  Its compulsory bytes per pixel: 36 of the current planes read, 36 of the previous
 planes gathered (the four taps of neighbouring pixels overlap: about one plane set of unique bytes), 16 of history, 8 of
 motion and 4 of RGBA8 written: 100.  `history_share` is the share of pixels that found history in the last frame.
+
+`temporal_dynamic` times rt_temporal_dynamic in the same loop, on the same planes into the same output plane: one sphere
+(hittable 4) is dragged back and forth, so every frame's scene is an rt_scene_edit of the one before and the motion
+table of rt_scene_motion (uploaded outside the timed region) holds a non-identity entry.  rt_temporal on those frames
+ignores the sphere's motion; its time is the yardstick (`ratio_to_temporal`).  The bytes are rt_temporal's: the table's
+80 bytes stay in cache.  --dynamic-json writes the two entries to a file (profiles/temporal_dynamic_bench.json).
 """
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -26,6 +32,7 @@ ap.add_argument("--warmup", type=int, default=12)
 ap.add_argument("--width", type=int, default=0, help="override the config's size (with --height)")
 ap.add_argument("--height", type=int, default=0)
 ap.add_argument("--texture-size", default="", help="WxH of the three textures (default: the config's 8192x4096)")
+ap.add_argument("--dynamic-json", default="", help="also write the temporal / temporal_dynamic entries to this file")
 args = ap.parse_args()
 
 cfg = scenes.CONFIGS["c5"]
@@ -33,8 +40,19 @@ if args.width and args.height:
     cfg = cfg.scaled(args.width, args.height)
 if args.texture_size:
     cfg.texture_size = tuple(int(v) for v in args.texture_size.split("x"))
-ds = DeviceScene(cfg.scene_desc())
+base_scene = cfg.scene_desc()
+ds = DeviceScene(base_scene)
 r = Renderer(cfg.width, cfg.height)
+
+
+def dragged(frame: int):
+    """The hittable list of `frame`: hittable 4 slides along a segment and back (12 steps each way)."""
+    k = abs(frame % 24 - 12)
+    h = type(base_scene.hittables).from_buffer_copy(base_scene.hittables)
+    h[4].center[:] = [1.5 - 0.08 * k, 0.0, 2.5 + 0.03 * k]
+    return h
+
+
 r.render_init()
 ITER = (1, 3, 5)
 npix = cfg.width * cfg.height
@@ -53,15 +71,32 @@ def timed(fn) -> float:
     return e0.elapsed_time(e1)
 
 
-times = {"render": [], "gbuffer": [], "temporal": [], **{f"denoise_n{n}": [] for n in ITER}}
+times = {"render": [], "gbuffer": [], "temporal": [], "temporal_dynamic": [], **{f"denoise_n{n}": [] for n in ITER}}
 total = args.warmup + args.frames
+hittables = dragged(0)
+history_share = {}
 for f in range(total):
     pos, fwd = scenes.moving_camera(f % 60, 60)
     inp = scenes.camera_inputs(pos, fwd, cfg.fov)
     r.reset_accumulation()
+    # the scene edit of this frame and its motion table, both outside the timed regions
+    previous, hittables = hittables, dragged(f)
+    ds, old = ds.edited(hittables), ds
+    old.close()
+    table = torch.from_numpy(scenes.scene_motion(previous, hittables)).to(r.device)
+    torch.cuda.synchronize()
     t = {"render": timed(lambda: r.render(ds, cfg.spp, cfg.depth, inp, flags=abi.RT_FLAG_ACCUMULATE, count=False)),
          "gbuffer": timed(lambda: r.gbuffer(ds, inp, keep_previous=True))}
-    t["temporal"] = timed(lambda: r.temporal(source="accum", motion=True))
+    # both passes on the same planes; which of the two runs first (and finds the caches cold) alternates by frame
+    calls = {"temporal": lambda: r.temporal(source="accum", motion=True),
+             "temporal_dynamic": lambda: r.temporal(source="accum", motion=True, prim_motion=table)}
+    order = ("temporal", "temporal_dynamic") if f % 2 == 0 else ("temporal_dynamic", "temporal")
+    for i, name in enumerate(order):
+        if i and r._history_spare is not None:  # (not the first frame) hand the planes back: the second call reads and
+            r.history, r._history_spare = r._history_spare, r.history  # writes what the first did
+        t[name] = timed(calls[name])
+        if f == total - 1:
+            history_share[name] = float((r.history[..., 3] > 1.0).float().mean().item())
     for n in ITER:
         t[f"denoise_n{n}"] = timed(lambda: r.denoise_async(iterations=n, source="accum"))
     if f >= args.warmup:
@@ -76,8 +111,18 @@ out["gbuffer"] = {"ms": round(ms["gbuffer"], 4), "bytes": gb, "GB_per_s": round(
                   "ratio_to_render": round(ms["gbuffer"] / ms["render"], 3)}
 tb = npix * 100
 out["temporal"] = {"ms": round(ms["temporal"], 4), "bytes": tb, "GB_per_s": round(tb / ms["temporal"] / 1e6, 1),
-                   "ratio_to_render": round(ms["temporal"] / ms["render"], 3),
-                   "history_share": round(float((r.history[..., 3] > 1.0).float().mean().item()), 3)}
+                   "ratio_to_render": round(ms["temporal"] / ms["render"], 3), "history_share": round(history_share["temporal"], 3)}
+out["temporal_dynamic"] = {"ms": round(ms["temporal_dynamic"], 4), "bytes": tb,
+                           "GB_per_s": round(tb / ms["temporal_dynamic"] / 1e6, 1),
+                           "ratio_to_render": round(ms["temporal_dynamic"] / ms["render"], 3),
+                           "ratio_to_temporal": round(ms["temporal_dynamic"] / ms["temporal"], 3),
+                           "history_share": round(history_share["temporal_dynamic"], 3),
+                           "table": [round(float(v), 4) for v in table[4].tolist()]}
+if args.dynamic_json:
+    with open(args.dynamic_json, "w") as fh:
+        json.dump({k: out[k] for k in ("config", "workload", "frames", "warmup", "device", "render_ms", "temporal",
+                                        "temporal_dynamic")}, fh)
+        fh.write("\n")
 for n in ITER:
     m, b = ms[f"denoise_n{n}"], denoise_bytes(n)
     out[f"denoise_n{n}"] = {"ms": round(m, 4), "bytes": b, "GB_per_s": round(b / m / 1e6, 1),

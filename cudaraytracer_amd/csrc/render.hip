@@ -313,6 +313,13 @@ struct Counts {
     // COUNT_TESTS (v3): idle lanes summed over node iterations: pixel done / ray finished, waiting for the
     // regeneration threshold / holding a leaf while the wave still visits nodes
     uint64_t idle_nt = 0, idle_fin = 0, idle_wait = 0;
+    // COUNT_TESTS (v3): node iterations by the lanes active in them (1, 2-4, 5-16, 17-64) and the node-uniform ones of
+    // each class (one lane is always uniform); uniform iterations before / after the first divergent iteration of
+    // their v3_traverse call
+    uint32_t vis1 = 0, vis4 = 0, vis16 = 0, vis64 = 0, uni4 = 0, uni16 = 0, uni64 = 0;
+    uint32_t uni_pre = 0, uni_post = 0;
+    // COUNT_TESTS (v3): stage 2 of bvh_clear: rays that enter it, rays it does not clear, shading passes with one
+    uint32_t s2_enter = 0, s2_fail = 0, s2_pass = 0;
 };
 
 // 1 on the lowest active lane of the wave, 0 elsewhere (diagnostic wave-iteration counts).
@@ -585,10 +592,12 @@ __device__ __forceinline__ bool bvh_odd_ray(const f3 ro, const f3 rd) {
 // q = p - c of a sphere hit (its normal's numerator).  (c) is tested only where it can matter: stage 1 of a sphere hit
 // needs no finite 1/d (a zero or tiny component leaves its axis unconstrained in AABB::Hit: an infinite slab; NaNs fail
 // its comparisons), a rectangle hit needs its plane axis' RN(1/d) to be rcp_rn's, stage 2 needs every axis'; and a
-// miss can be a NaN hit of the reference's only in a scene with rectangles.
+// miss can be a NaN hit of the reference's only in a scene with rectangles.  s2 (counting builds): [0] += 1 for a ray
+// that enters stage 2, [1] += 1 if stage 2 does not clear it.
 template <class PP>
 __device__ __forceinline__ bool bvh_clear(PP P, int& hit, const uint32_t tag, const float t, const f3 ro, const f3 rd,
-                                          const float4 p0, const float4 p1, const f3 td, const f3 p, const f3 q) {
+                                          const float4 p0, const float4 p1, const f3 td, const f3 p, const f3 q,
+                                          uint32_t* const s2 = nullptr) {
     // flags in bits 29-31 of the hit index: 000 a hit, 010 a tie, 001 verified, 111 a miss (-1); kVerifiedMiss
     const uint32_t flags = (uint32_t)hit >> 29;
     const bool miss = hit < 0 || hit == kVerifiedMiss, tie = flags == 2u, verified = flags == 1u;
@@ -619,9 +628,13 @@ __device__ __forceinline__ bool bvh_clear(PP P, int& hit, const uint32_t tag, co
                     (p1.x - pb) > m && (neg ? s1 : s0) < t && (neg ? s0 : s1) > t;
         }
         if (__builtin_expect(!clear && !tie && t > kTmin && !bvh_odd_ray(ro, rd), 0)) {
-            // stage 2 (rare): AABB::Hit(own box, 0.001, t*) with the reference's arithmetic
+            // stage 2: AABB::Hit(own box, 0.001, t*) with the reference's arithmetic.  Not rare where a large sphere
+            // is seen near a pole (|q_a| within r·2^-19 of r): 0.6 % of C2's rays, one in 6.8 % of its shading passes
+            // (profiles/r07a_visit_uniformity_c2.txt).  A sphere's box formed from the hit record instead of the
+            // table's two loads measured slower (C2 +0.6 %, profiles/r07b_ab_visit_c2.txt).
             const float4* boxes = P->bvh_boxes;
             clear = ref_box(boxes[2 * hit], boxes[2 * hit + 1], ro, mk(rcp_rn(rd.x), rcp_rn(rd.y), rcp_rn(rd.z)), t);
+            if (s2) s2[0]++, s2[1] += clear ? 0u : 1u;
         }
     }
     if (RT_BVH_EXACT == 2) {  // (A/B builds: the check without the replay)
@@ -872,7 +885,7 @@ enum { SHADE_REPLAY = 3 };
 template <bool TEX = true, bool DEFER = false, bool EXACT = false, class PP, class R>
 __device__ __forceinline__ int shade(PP P, const float4* __restrict__ prims, const float4* __restrict__ mats,
                                      const int4* __restrict__ imgs, int hit, uint32_t hit_tag, float t,
-                                     f3& ro, f3& rd, f3& att, R& rng, bool rtl, f3& contrib) {
+                                     f3& ro, f3& rd, f3& att, R& rng, bool rtl, f3& contrib, uint32_t* const s2 = nullptr) {
     float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = p0;
     // unit_vector(rd) is needed by the sky (y only), Metal and Dielectric: computed once for all lanes of
     // the wave that need it instead of once per material branch (same binary32 operations, Math.cuh:210-213)
@@ -889,7 +902,7 @@ __device__ __forceinline__ int shade(PP P, const float4* __restrict__ prims, con
         if (hit >= 0 && hit != kVerifiedMiss) mword = __float_as_uint(mats[3 * (hit_tag >> 4)].x);
         const f3 td = scale(t, rd);  // (the hit point and p - c: shared with the hit record below)
         const f3 ph = add(ro, td);
-        if (__builtin_expect(!bvh_clear(P, hit, hit_tag, t, ro, rd, p0, p1, td, ph, sub(ph, xyz(p0))), 0)) return SHADE_REPLAY;
+        if (__builtin_expect(!bvh_clear(P, hit, hit_tag, t, ro, rd, p0, p1, td, ph, sub(ph, xyz(p0)), s2), 0)) return SHADE_REPLAY;
         mtype = hit >= 0 ? (mword & 15u) : 0xffu;
     } else {
         if (hit >= 0) mtype = __float_as_uint(mats[3 * (hit_tag >> 4)].x) & 15u;
@@ -1086,6 +1099,17 @@ __device__ __forceinline__ void flush_counts(const KParams& P, const Counts& cnt
             atomicAdd(&P.counters[15], (unsigned long long)cnt.idle_wait);
             atomicAdd(&P.counters[16], (unsigned long long)cnt.rects);
             atomicAdd(&P.counters[17], (unsigned long long)cnt.replays);
+            // words 18-23 hold two 32-bit counts each (low | high << 32; a frame whose count passes 2^32 carries
+            // into its neighbour): 18 one-lane node iterations | stage-2 failures, 19-21 node iterations with 2-4 /
+            // 5-16 / 17-64 lanes | the uniform ones, 22 uniform iterations before | after the call's first
+            // divergent one, 23 stage-2 entries | shading passes with one
+            const auto two = [](uint32_t lo, uint32_t hi) { return (unsigned long long)lo | (unsigned long long)hi << 32; };
+            atomicAdd(&P.counters[18], two(cnt.vis1, cnt.s2_fail));
+            atomicAdd(&P.counters[19], two(cnt.vis4, cnt.uni4));
+            atomicAdd(&P.counters[20], two(cnt.vis16, cnt.uni16));
+            atomicAdd(&P.counters[21], two(cnt.vis64, cnt.uni64));
+            atomicAdd(&P.counters[22], two(cnt.uni_pre, cnt.uni_post));
+            atomicAdd(&P.counters[23], two(cnt.s2_enter, cnt.s2_pass));
             if (cnt.ctotal && wave_leader()) {  // one lane per wave: the stamps are wave-uniform
                 atomicAdd(&P.counters[7], (unsigned long long)cnt.ctrav);
                 atomicAdd(&P.counters[8], (unsigned long long)cnt.cshade);
@@ -1830,14 +1854,23 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
     constexpr uint32_t stk_off = STK_OFF / sizeof(Entry);  // in entries
     const float tmin_s = kTmin;  // an SGPR operand of the slab test's v_max
     const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc((void*)prims, (short)0, 0x7fffffff, 0x00020000);
+    bool seen_div = false;  // COUNT_TESTS: this call has had a node iteration whose lanes held different nodes
+    // Every node iteration of this call so far had all its lanes on one node (the 48-B tables' scalar path).  A
+    // wave-level fact held per lane and made uniform again at each node phase's start (a lane that waited with its
+    // leaf through the first divergent iteration learns of it there): read and written per node phase, not per visit.
+    bool coh = NODES != NODES_64;
     while (node != RW::kSentinel || leaf >= RW::kLeaf) {
         // t_best changes only in the leaf phase: canonicalised once here, not on every visit by fminf
         const float t_best_c = __builtin_canonicalizef(t_best);
         const uint32_t n_outer = COUNT_TESTS ? (uint32_t)__popcll(__ballot(1)) : 0u;  // lanes still tracing
         (void)n_outer;
+        // (a lane that waited with its leaf through a divergent iteration learns of it here)
+        if (COUNT_TESTS) seen_div = __ballot(seen_div) != 0;
         // lanes holding no leaf yet, carried through the visits as an SGPR mask
         uint64_t lzm = __ballot(leaf == 0);
-        while (node < RW::kSentinel) {
+        // One node visit of the lanes with node < kSentinel.  scalar: they all hold node nu, which is then read through
+        // the constant cache.  Returns whether the node loop ends here for the leaf tests (RT_TUNE_LEAF_BREAK).
+        const auto visit = [&](const bool scalar, const uint32_t nu) __attribute__((always_inline)) -> bool {
             // the entry address as one v_lshl_add_u32 (LLVM emits a half-rate shift plus an add: C2 −0.2 %,
             // C3 −0.3 %, profiles/r02e_ab_stack_addr.txt)
             uint32_t sa;
@@ -1886,8 +1919,7 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
                      __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(nrsrc, noff + 16u, 0, 0)),
                      __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(nrsrc, noff + 32u, 0, 0)));
             } else {  // 48 B of f32 boxes + 4 B of references
-                const uint32_t nu = __builtin_amdgcn_readfirstlane(node);
-                if (__ballot(node != nu) == 0) {
+                if (scalar) {
                     // every active lane visits the same node: scalar loads through the constant cache, planes as
                     // SGPR operands of the FMAs — no vector-memory (TA/TD) traffic, the kernel's busiest unit
                     const ConstF32* cn = (const ConstF32*)((const ConstU8*)nodes_tab + nu * 48u);
@@ -1934,8 +1966,19 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
             if (COUNT_TESTS) {
                 cnt.boxes += 2;
                 cnt.wnode += wave_leader();
-                if (__ballot(node != (uint32_t)__builtin_amdgcn_readfirstlane(node)) == 0) cnt.wnode_uniform += wave_leader();
-                const uint32_t act = (uint32_t)__popcll(__ballot(1));
+                const bool uni = __ballot(node != (uint32_t)__builtin_amdgcn_readfirstlane(node)) == 0;
+                const uint32_t act = (uint32_t)__popcll(__ballot(1)), lead = wave_leader();
+                if (uni) {
+                    cnt.wnode_uniform += lead;
+                    if (seen_div) cnt.uni_post += lead;
+                    else cnt.uni_pre += lead;
+                } else {
+                    seen_div = true;
+                }
+                if (act == 1u) cnt.vis1 += lead;
+                else if (act <= 4u) cnt.vis4 += lead, cnt.uni4 += uni ? lead : 0u;
+                else if (act <= 16u) cnt.vis16 += lead, cnt.uni16 += uni ? lead : 0u;
+                else cnt.vis64 += lead, cnt.uni64 += uni ? lead : 0u;
                 if (wave_leader()) {
                     cnt.idle_nt += 64u - ntrav;
                     cnt.idle_fin += ntrav - n_outer;
@@ -1986,7 +2029,35 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
                       [ch1] "v"(ch1), [t1] "v"(top1), [t2] "v"(top2), [sent] "s"(RW::kSentinel));
                 (void)m0; (void)m2; (void)m3;
                 *sp_entry = (Entry)farc;
-                if ((uint32_t)__popcll(m5) <= leaf_break) break;  // (RT_TUNE_LEAF_BREAK)
+                return (uint32_t)__popcll(m5) <= leaf_break;  // (RT_TUNE_LEAF_BREAK)
+            }
+        };
+        // The uniform-node check — a v_readfirstlane and a v_cmp, 8 issue cycles — is made only until the call's
+        // first divergent iteration: the first loop holds the scalar visits of the call's coherent prefix and
+        // leaves without a visit when the lanes' nodes differ, the second visits without the check.  On C2 61 % of
+        // the uniform iterations lie in that prefix (profiles/r07a_visit_uniformity_c2.txt); the others now take the
+        // vector path, and 84 % of all iterations no longer pay for the check: C2 −2 %
+        // (profiles/r07b_ab_visit_c2.txt).  The state is the loop a wave is in, not a flag tested per visit (as a
+        // flag LLVM keeps it in a VGPR and re-reads it per visit); checking again at each node phase's start
+        // measured −0.9 % only, and a cheaper hand-over of `coh` between node phases, after which LLVM compiles the
+        // second loop top-tested, measured slower than no split at all: time any change to this shape.
+        if constexpr (NODES != NODES_64) coh = __ballot(!coh) == 0;
+        if (coh) {
+            while (node < RW::kSentinel) {
+                const uint32_t nu = __builtin_amdgcn_readfirstlane(node);
+                if (__ballot(node != nu) != 0) {
+                    coh = false;
+                    break;
+                }
+                if (visit(true, nu)) break;
+            }
+        }
+        if (!coh) {
+            // (taken again after the first loop: a mask carried out of a loop its lanes leave one by one would live
+            // in a VGPR)
+            if constexpr (NODES != NODES_64) lzm = __ballot(leaf == 0);
+            while (node < RW::kSentinel) {
+                if (visit(false, 0u)) break;
             }
         }
         const uint64_t t_leaf = COUNT_TESTS ? __builtin_amdgcn_s_memtime() : 0;
@@ -2186,8 +2257,14 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
                 f3 contrib;
                 if (COUNT_TESTS) cnt.wshade += wave_leader();
                 KParamsC* const q = kparams_reload();
+                uint32_t s2[2] = {0u, 0u};
                 const int res = shade<TEX, false, true>(q, prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att, rng,
-                                                        rtl, contrib);
+                                                        rtl, contrib, COUNT_TESTS ? s2 : nullptr);
+                if (COUNT_TESTS) {
+                    cnt.s2_enter += s2[0];
+                    cnt.s2_fail += s2[1];
+                    if (__ballot(s2[0] != 0u) != 0) cnt.s2_pass += wave_leader();
+                }
                 bool ended = res == SHADE_ENDED;
                 if (res != SHADE_REPLAY && !ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
                     ended = true;

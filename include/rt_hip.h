@@ -307,7 +307,7 @@ typedef struct rt_render_args {
     float* accum;             /* RT_FLAG_ACCUMULATE: device float4 running sum of samples */
     rt_curand_state* state;   /* device RNG states, local_rows × width (RT_FLAG_STATE_SOA: the six planes) */
     uint64_t* counters;       /* optional device uint64[RT_COUNTERS_WORDS] with RT_FLAG_COUNT_TESTS (the
-                                 kernels then write up to word 17; ABI versions < 6 wrote 16 words: see
+                                 kernels then write up to word 23; ABI versions < 6 wrote 16 words: see
                                  rt_abi_version), else uint64[16]: rays, box tests, primitive tests, primary samples;
                                  with RT_FLAG_COUNT_TESTS
                                  also [4..6] = wave-level iterations of node visits,
@@ -318,7 +318,13 @@ typedef struct rt_render_args {
                                  (pixel done, ray finished, holding a leaf), [16] = rectangle tests (the
                                  part of [2] that are XY/XZ/YZRect::Hit; the FLOP model prices them apart),
                                  [17] = rays whose closest hit the exactness check replayed through the
-                                 reference BVH (render.hip bvh_clear / flat_trace) */
+                                 reference BVH (render.hip bvh_clear / flat_trace); the v3 kernels also
+                                 [18..23], two 32-bit counts per word (low | high << 32): [18] = one-lane
+                                 node iterations | rays stage 2 of bvh_clear did not clear, [19..21] = node
+                                 iterations with 2-4 / 5-16 / 17-64 active lanes | the node-uniform ones,
+                                 [22] = uniform node iterations before | after their traversal call's first
+                                 divergent one, [23] = rays entering stage 2 | shading passes with such a
+                                 ray (tools/visit_uniformity.py) */
     uint32_t width;
     uint32_t height;          /* global image height */
     uint32_t samples_per_pixel;

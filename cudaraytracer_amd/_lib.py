@@ -9,7 +9,7 @@ import os
 
 from . import abi
 
-LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librt_hip.so")
+LIB_PATH = _IN_TREE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "librt_hip.so")
 # A/B experiments only: RT_HIP_LIB names another in-tree build of the same library (tools/ab_builds.sh).
 LIB_PATH = os.environ.get("RT_HIP_LIB", LIB_PATH)
 
@@ -65,6 +65,7 @@ EXPORTED = [
     "rt_procedural_texture",
     "rt_reference_graph_flatten",
     "rt_build_host_tables",
+    "rt_tile_entries_host",
 ]
 
 _lib = None
@@ -130,6 +131,9 @@ def _declare(lib: C.CDLL) -> None:
                                                P(C.c_uint32), P(abi.ImageDesc), P(C.c_uint32)]
     lib.rt_build_host_tables.argtypes = [P(abi.SceneDesc), P(C.c_float), P(C.c_float), P(C.c_float),
                                          P(C.c_int32), P(abi.HostTablesInfo)]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_tile_entries_host"):  # (an A/B build of an older revision lacks it)
+        lib.rt_tile_entries_host.argtypes = [P(abi.SceneDesc), P(abi.InputStruct), C.c_uint32, C.c_uint32, P(abi.Tiling),
+                                             C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32)]
     lib.LaunchKernel.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, abi.InputStruct]
     lib.LaunchKernel.restype = None
     lib.LaunchRandInit.argtypes = [vp]

@@ -26,7 +26,7 @@ RT_DENOISE_DEMODULATE = 1 << 0
 RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
 RT_TEMPORAL_RESET = 1 << 1
-ABI_VERSION = 9  # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit
+ABI_VERSION = 10  # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
 MOTION_IDENTITY = (0.0, 0.0, 0.0, 1.0)
@@ -48,6 +48,7 @@ RT_TUNE_QUEUE_RESET = 21  # 1 = rt_render memsets the persistent queue slot per 
 RT_TUNE_GROUP_CHUNK = 22  # ... positions per chunk of the workgroup chunk queue (group mode 2)
 RT_TUNE_GROUP_LINGER_US = 23  # ... a finished workgroup waits this long (us) for the grid's others before exiting
 RT_TUNE_GROUP_WAVES = 24  # ... waves per workgroup of the persistent flat kernel's group builds (4/8/12/16)
+RT_TUNE_TILE_ENTRIES = 25  # v3: camera rays start at their tile's candidate leaves (1) or at the root (0)
 RT_TUNE_GROUP_TAIL = 19  # ... permille of the tiles left to the per-wave queue behind the shares
 
 STATUS = {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <new>
@@ -86,6 +87,8 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     s->host = h;
     s->host.texels = std::vector<uint8_t>();  // uploaded below (or shared); no host copy is kept
     DeviceScene& d = s->dev;
+    static std::atomic<uint64_t> next_uid{1};
+    d.uid = next_uid.fetch_add(1);
     int rc;
     void* p;
     if ((rc = upload(h.nodes, &p, "hipMalloc/hipMemcpy(nodes)"))) goto fail;

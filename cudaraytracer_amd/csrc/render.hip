@@ -38,6 +38,7 @@
 #include "rt_epilogue.h"
 #include "rt_internal.h"
 #include "rt_scene_device.h"
+#include "rt_tile_entry.h"
 
 namespace rt {
 namespace dev {
@@ -275,6 +276,8 @@ struct KParams {
     uint32_t linger_ticks;           // persistent flat, GROUP: a finished workgroup waits at most this long (100 MHz
                                      // ticks) for the grid's others before it exits (group_linger; 0: it does not)
     uint32_t group_chunk;            // ... positions per chunk (a multiple of 64)
+    const uint4* tile_entries;       // v3 (16-bit references): per tile its entry record (rt_tile_entry.h), NULL = every
+                                     // camera ray starts at the root (RT_TUNE_TILE_ENTRIES 0)
 };
 
 constexpr int kStackMax = 64;
@@ -1711,11 +1714,52 @@ __device__ __forceinline__ void v3_start_trace(uint32_t num_nodes, Cursor& c, ui
     c.mode = MODE_TRAV;
 }
 
+// A camera ray of tile `tile` (wave-uniform) starts its traversal (v3).  With an entry table (q->tile_entries,
+// rt_tile_entry.h) the ray starts at the leaves — or parts of leaves, runs of primitives in a leaf reference's form —
+// that its tile's beam can touch instead of the root: entry 0 is the lane's
+// postponed leaf, entry 1 its `node` (a leaf reference or the sentinel) and the rest its stack from kStackBase, so
+// v3_traverse's leaf loop walks the chain — a leaf reference in `node`, then those on the stack — without a node visit,
+// and the sentinel pads end it.  (`node` holds a leaf reference only while `leaf` does: a record without leaves gives
+// leaf = 0, node = sentinel, a finished traversal that missed.)  The record is read with a scalar load here, where
+// it is used, and is not held through the loop.
+// Exactness: the candidates hold every primitive that can meet the tile's padded beam, so every primitive whose
+// test can accept the ray is tested and the geometric closest hit is the root traversal's; the leaf tests set kTieBit
+// whatever the order they run in; and bvh_clear / ref_trace_wave, which decide whether that hit is the reference's,
+// read the hit record, bvh_boxes and the reference tables (bvh_ref_nodes, bvh_ref_pairs) only — never this tree.
+template <bool WIDE>
+__device__ __forceinline__ void v3_start_camera_trace(KParamsC* q, const uint32_t tile, typename RefW<WIDE>::Entry* const stk,
+                                                      Cursor& c, uint32_t& rays) {
+    v3_start_trace<WIDE>(q->num_nodes, c, rays);
+    if constexpr (!WIDE) {
+        typedef const __attribute__((address_space(4))) uint32_t ConstWord;
+        ConstWord* const tab = (ConstWord*)q->tile_entries;
+        if (tab) {
+            ConstWord* const r = tab + 4u * (size_t)__builtin_amdgcn_readfirstlane(tile);  // (one s_load_dwordx4)
+            const uint32_t rx = r[0], ry = r[1], rz = r[2], rw = r[3];
+            const uint32_t e0 = rx & 0xffffu;
+            if (e0 != kTileEntryRoot) {
+                c.leaf = e0 == kTileEntryNone ? 0 : (int)e0;
+                c.node = (int)(rx >> 16);
+                const uint32_t e[6] = {ry & 0xffffu, ry >> 16, rz & 0xffffu, rz >> 16, rw & 0xffffu, rw >> 16};
+                uint32_t n = 0;
+#pragma unroll
+                for (int i = 0; i < 6; i++)
+                    if (e[i] != kTileEntryNone) {  // (wave-uniform; the entries are packed from the front)
+                        stk[(kStackBase + i) * 64] = (typename RefW<WIDE>::Entry)e[i];
+                        n = (uint32_t)i + 1u;
+                    }
+                c.sp = kStackBase + n;
+            }
+        }
+    }
+}
+
 // A path ended with `contrib`: accumulate (Kernel.cu:147), then the next sample's camera ray, or finish.
 template <bool WIDE, class R>
 __device__ __forceinline__ void v3_next_sample(const KParams& P, uint32_t x, uint32_t g, f3 contrib, R& rng,
                                                f3& col, f3& att, uint32_t& sample, uint32_t& depth, f3& ro,
-                                               f3& rd, Cursor& c, uint32_t& rays) {
+                                               f3& rd, Cursor& c, uint32_t& rays, const uint32_t tile,
+                                               typename RefW<WIDE>::Entry* const stk) {
     col = add_sample(rng, col, contrib);
     KParamsC* q = kparams_reload();  // (launch-uniform operands re-read here, not held in SGPRs through the loop)
     const Camera cam = lane_camera(q, x, g);
@@ -1724,7 +1768,7 @@ __device__ __forceinline__ void v3_next_sample(const KParams& P, uint32_t x, uin
         att = mk(1.0f, 1.0f, 1.0f);
         depth = 0;
         if (q->max_depth > 0) {
-            v3_start_trace<WIDE>(q->num_nodes, c, rays);
+            v3_start_camera_trace<WIDE>(q, tile, stk, c, rays);
             return;
         }
         col = add_sample(rng, col, mk(0.0f, 0.0f, 0.0f));  // exceeded recursion (Kernel.cu:79)
@@ -2221,7 +2265,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
         // (sample = -1: v3_next_sample starts sample 0; with spp = 0 it stays 0, so compact parking's packed
         // sample field cannot spill into the ray count)
         uint32_t sample = P.spp > 0 ? (uint32_t)-1 : 0u, depth = 0, rays = 0;
-        if (P.spp > 0) v3_next_sample<WIDE>(P, x, g, mk(0.0f, 0.0f, 0.0f), rng, col, att, sample, depth, ro, rd, c, rays);
+        if (P.spp > 0) v3_next_sample<WIDE>(P, x, g, mk(0.0f, 0.0f, 0.0f), rng, col, att, sample, depth, ro, rd, c, rays, tile, stk);
         v3_park<COMPACT>(park, rng, col, att, items ? lane : sample, depth, rays);  // (col + 0 = +0 above)
         if (kItemsBuild && items) {  // (after the park above, which wrote colour words)
             park[1 * 64] = park[2 * 64] = park[3 * 64] = park[4 * 64] = 0u;
@@ -2283,7 +2327,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
                 } else if (ended) {  // the colour sum stays parked until a path ends (3 fewer VGPRs live through shade())
                     col = mk(__uint_as_float(park[(PK_COL + 0) * 64]), __uint_as_float(park[(PK_COL + 1) * 64]),
                              __uint_as_float(park[(PK_COL + 2) * 64]));
-                    v3_next_sample<WIDE>(P, x, g, contrib, rng, col, att, sample, depth, ro, rd, c, rays);
+                    v3_next_sample<WIDE>(P, x, g, contrib, rng, col, att, sample, depth, ro, rd, c, rays, tile, stk);
                     park[(PK_COL + 0) * 64] = __float_as_uint(col.x);
                     park[(PK_COL + 1) * 64] = __float_as_uint(col.y);
                     park[(PK_COL + 2) * 64] = __float_as_uint(col.z);
@@ -2313,7 +2357,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
                         KParamsC* q = kparams_reload();
                         camera_ray(q, lane_camera(q, px, pg), rng, ro, rd, item >> 6);
                         uint32_t rays = 0u;
-                        v3_start_trace<WIDE>(P.num_nodes, c, rays);
+                        v3_start_camera_trace<WIDE>(q, tile, stk, c, rays);  // (the item's pixel lies in this tile)
                         v3_park<COMPACT, false>(park, rng, mk(0.0f, 0.0f, 0.0f), mk(1.0f, 1.0f, 1.0f), p, 0u, rays);
                     } else {
                         c.mode = MODE_DONE;
@@ -3692,6 +3736,15 @@ __global__ __launch_bounds__(1024) void plan_order_kernel(const uint32_t* __rest
     for (uint32_t i = threadIdx.x; i < n; i += 1024u) order[atomicAdd(&start[cost_bucket(cost[i])], 1u)] = i;
 }
 
+// Pre-pass of the v3 kernels: the entry record of every tile (rt_tile_entry.h), one lane per tile.  Bounds: a lane
+// writes out[tile] only for tile < n, the table's size; tile_record reads node records below F.num_nodes and primitive
+// records below F.num_prims only.
+__global__ __launch_bounds__(64) void tile_entries_kernel(const float* __restrict__ nodes, const float* __restrict__ prims,
+                                                          const TileFrame F, TileRecord* __restrict__ out, const uint32_t n) {
+    const uint32_t tile = blockIdx.x * 64u + threadIdx.x;
+    if (tile < n) out[tile] = tile_record(nodes, prims, F, tile);
+}
+
 __global__ void rand_init_kernel(uint32_t* state) {  // RandInit (Kernel.cu:160-164)
     if (threadIdx.x == 0 && blockIdx.x == 0) curand_init_state(1984ull, state);
 }
@@ -3953,6 +4006,79 @@ int acquire_plan(const PlanKey& key, hipStream_t s, std::shared_ptr<TilePlan>* o
     *out = it->second;
     return RT_OK;
 }
+// RT_TUNE_TILE_ENTRIES: 1 (default) = the v3 kernels start a full tile's camera rays at the tile's candidate leaves
+// (rt_tile_entry.h; 16-bit-reference scenes, band_rows a multiple of 8), 0 = every ray starts at the root (A/B, tests)
+thread_local int g_tile_entries = 1;
+
+// Per (device, stream, tile grid): the tiles' entry records and what they were filled for.  The pre-pass runs again
+// only when the scene, the camera terms, the frame shape or the band layout differ from the launch that filled the
+// table: a still camera accumulating frames pays it once, a moving one every frame (~15 node records per tile).
+// mu is held from the comparison until the render launch that reads the table is enqueued, so a second thread on the
+// same stream cannot refill the table between this launch's pre-pass and its render kernel.
+struct EntryTable {
+    TileRecord* rec = nullptr;
+    std::mutex mu;
+    bool filled = false;
+    uint64_t scene_uid = 0;
+    TileFrame frame;
+    ~EntryTable() {
+        if (rec) (void)hipFree(rec);
+    }
+};
+// never destroyed (frees device memory, see g_plans)
+std::map<std::tuple<int, void*, uint32_t, uint32_t>, std::shared_ptr<EntryTable>>& g_entry_tables =
+    *new std::map<std::tuple<int, void*, uint32_t, uint32_t>, std::shared_ptr<EntryTable>>();
+std::mutex g_entry_tables_mu;
+
+int acquire_entry_table(int device, hipStream_t s, uint32_t tiles_x, uint32_t tiles, std::shared_ptr<EntryTable>* out) {
+    std::lock_guard<std::mutex> lock(g_entry_tables_mu);
+    const auto key = std::make_tuple(device, (void*)s, tiles_x, tiles);
+    auto it = g_entry_tables.find(key);
+    if (it == g_entry_tables.end()) {
+        if (g_entry_tables.size() >= kMaxPlans) g_entry_tables.clear();  // holders keep their tables alive
+        auto t = std::make_shared<EntryTable>();
+        void* r = nullptr;
+        const int rc = hip_check(hipMalloc(&r, (size_t)tiles * sizeof(TileRecord)), "rt_render: tile entry allocation");
+        if (rc != RT_OK) return rc;
+        t->rec = (TileRecord*)r;
+        it = g_entry_tables.emplace(key, std::move(t)).first;
+    }
+    *out = it->second;
+    return RT_OK;
+}
+
+// The classifier's view of a launch (P's camera terms and frame shape are set; P.tiles_x is the 8×8 tile grid's).
+// depth: the BVH's — the v3 stack holds `depth` entries above its pads, and a record's entries 2… go there.
+TileFrame tile_frame_of(const dev::KParams& P, const bool wide_refs, const uint32_t depth) {
+    TileFrame F;
+    std::memset(&F, 0, sizeof(F));  // (compared bytewise, EntryTable::frame)
+    for (int i = 0; i < 3; i++) {
+        F.origin[i] = P.origin[i];
+        F.up[i] = P.up[i];
+        F.right[i] = P.right[i];
+        F.fov_fwd[i] = P.fov_fwd[i];
+        F.k10_fwd[i] = P.k10_fwd[i];
+    }
+    F.near_plane = P.near_plane;
+    F.far_plane = P.far_plane;
+    F.width_f = P.width_f;
+    F.cx = P.cx;
+    F.cy = P.cy;
+    F.width = P.width;
+    F.local_rows = P.local_rows;
+    F.band_rows = P.band_rows;
+    F.num_ranks = P.num_ranks;
+    F.rank = P.rank;
+    F.grid_w = P.grid_w;
+    F.grid_h = P.grid_h;
+    F.tiles_x = P.tiles_x;
+    F.num_nodes = P.num_nodes;
+    F.num_prims = P.num_prims;
+    F.wide_refs = wide_refs ? 1u : 0u;
+    F.max_entries = std::min<uint32_t>(kTileEntryMax, depth + 2u);
+    return F;
+}
+
 thread_local int g_persistent_waves = 0;  // 0: occupancy query
 
 constexpr size_t kLdsLimit = 160 * 1024;
@@ -4096,6 +4222,58 @@ static void fill_camera(dev::KParams& P, const rt_input_struct& in, const uint32
             P.bg1[i] = in.background_end[i];
         }
     }
+}
+
+// The entry records rt_render's pre-pass would write for these tiles, by the same classifier on the host (no device).
+int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* inputs, uint32_t width, uint32_t height,
+                         const rt_tiling* tiling, uint32_t flags, uint32_t first_tile, uint32_t num_tiles,
+                         uint32_t* records) {
+    if (!desc || !inputs || !tiling || (num_tiles && !records)) {
+        set_error("rt_tile_entries_host: NULL argument");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (tiling->band_rows == 0 || tiling->num_ranks == 0 || tiling->rank >= tiling->num_ranks || width == 0 || height == 0) {
+        set_error("rt_tile_entries_host: invalid frame or tiling");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    HostScene h;
+    try {
+        std::string err;
+        const int rc = build_host_scene(desc, &h, &err, false);
+        if (rc != RT_OK) {
+            set_error("rt_tile_entries_host: " + err);
+            return rc;
+        }
+    } catch (const std::exception& e) {
+        set_error(std::string("rt_tile_entries_host: ") + e.what());
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    dev::KParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.num_nodes = h.num_nodes;
+    P.num_prims = h.num_prims;
+    P.width = width;
+    P.height = height;
+    P.band_rows = tiling->band_rows;
+    P.num_ranks = tiling->num_ranks;
+    P.rank = tiling->rank;
+    P.local_rows = tiling->local_rows;
+    const bool faithful = (flags & RT_FLAG_FAITHFUL_GRID) != 0;
+    P.grid_w = faithful ? (width / 16) * 16 : width;
+    P.grid_h = faithful ? (height / 16) * 16 : height;
+    P.tiles_x = (width + 7u) / 8u;
+    fill_camera(P, *inputs, width, height);
+    const uint64_t tiles = (uint64_t)P.tiles_x * ((tiling->local_rows + 7u) / 8u);
+    if ((uint64_t)first_tile + num_tiles > tiles) {
+        set_error("rt_tile_entries_host: tiles outside the frame");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const TileFrame F = tile_frame_of(P, h.wide_refs, h.depth);
+    for (uint32_t i = 0; i < num_tiles; i++) {
+        const TileRecord r = tile_record(h.nodes.data(), h.prims.data(), F, first_tile + i);
+        std::memcpy(records + 4 * (size_t)i, r.w, 16);
+    }
+    return RT_OK;
 }
 
 int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t* hits, uint64_t* counters,
@@ -4448,6 +4626,15 @@ int rt_set_tuning(int key, int value) {
         g_persistent_waves = value;
         return prev;
     }
+    if (key == RT_TUNE_TILE_ENTRIES) {
+        if (value < 0 || value > 1) {
+            set_error("rt_set_tuning: tile entries must be 0 or 1");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        int prev = g_tile_entries;
+        g_tile_entries = value;
+        return prev;
+    }
     set_error("rt_set_tuning: unknown key");
     return RT_ERR_INVALID_ARGUMENT;
 }
@@ -4754,10 +4941,35 @@ int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) 
         (void)hipEventRecord(e0, s);
     }
     g_last_variant = variant;
+    // v3 on a 16-bit-reference scene: the tiles' entry records, refilled when what they were computed from changed
+    std::shared_ptr<EntryTable> entries;
+    std::unique_lock<std::mutex> entries_lock;
+    if (V.kernel == 3 && !wide && !S.wide_refs && g_tile_entries && S.num_nodes > 0 && S.nodes && T.band_rows % 8u == 0 &&
+        a->samples_per_pixel > 0 && a->max_depth > 0) {
+        int device = 0;
+        int rc = hip_check(hipGetDevice(&device), "rt_render: hipGetDevice");
+        if (rc == RT_OK) rc = acquire_entry_table(device, s, P.tiles_x, tiles, &entries);
+        if (rc != RT_OK) return rc;
+        entries_lock = std::unique_lock<std::mutex>(entries->mu);
+        const TileFrame F = tile_frame_of(P, S.wide_refs, S.depth);
+        if (!entries->filled || entries->scene_uid != S.uid || std::memcmp(&entries->frame, &F, sizeof(F)) != 0) {
+            (void)hipGetLastError();
+            entries->filled = false;
+            hipLaunchKernelGGL(dev::tile_entries_kernel, dim3((tiles + 63u) / 64u), dim3(64), 0, s, (const float*)S.nodes,
+                               (const float*)S.prims, F, entries->rec, tiles);
+            rc = hip_check(hipGetLastError(), "rt_render: tile entry kernel launch", RT_ERR_LAUNCH);
+            if (rc != RT_OK) return rc;
+            entries->filled = true;
+            entries->scene_uid = S.uid;
+            entries->frame = F;
+        }
+        P.tile_entries = (const uint4*)entries->rec;
+    }
     if (trial) (void)hipEventRecord(trial->ev[trial_slot], s);
     (void)hipGetLastError();
     hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds_bytes, s, P);
     int rc = hip_check(hipGetLastError(), "rt_render: kernel launch", RT_ERR_LAUNCH);
+    if (entries_lock.owns_lock()) entries_lock.unlock();
     // A persistent launch that did not run leaves its queue slot as it found it, but the slot is re-zeroed anyway, so
     // that the launch reusing it kQueueSlots launches later never finds exhausted heads (the slot is
     // otherwise clean only because the grid's last wave zeroes it in queue_release)

@@ -33,6 +33,7 @@ struct DeviceScene {
     bool has_textures = false;  // any CHECKER or IMAGE albedo (selects the texture-capable kernel)
     bool has_rects = false;     // HostScene::has_rects
     uint64_t device_bytes = 0;
+    uint64_t uid = 0;  // unique per created device scene (a handle's address can be reused; render.hip EntryTable)
 };
 
 // Upload the tables of `h` to the current device.  shared_texels: an existing device texel block (same image

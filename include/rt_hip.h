@@ -184,7 +184,7 @@ const char* rt_version(void);
  * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
  * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal.  9: rt_scene_motion, rt_temporal_dynamic,
  * rt_scene_edit. */
-#define RT_ABI_VERSION 9
+#define RT_ABI_VERSION 10
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -614,7 +614,11 @@ int rt_last_variant(void);
  *   has (waves exiting while others render stall them), at most this long (0..100000; default 0 = exit at once: the
  *   groups' simultaneous exit then costs the kernel's end ~100 us, more than the stall it avoids).
  *   RT_TUNE_GROUP_WAVES: waves per workgroup of those builds (4, 8, 12 or 16, default 16; the grid keeps 4 waves per
- *   SIMD where the group size divides 16, else the one group per CU that fits). */
+ *   SIMD where the group size divides 16, else the one group per CU that fits).
+ *   RT_TUNE_TILE_ENTRIES: 1 (default) = the v3 kernels (variants 2, 3) start the camera rays of a full 8x8 tile at the
+ *   BVH leaves the tile's beam can touch, from a per-tile table a pre-pass fills when the scene, the camera, the frame
+ *   shape or the band layout changed (rt_tile_entries_host; scenes with 16-bit references and band_rows a multiple of
+ *   8); 0 = every ray starts at the root.  Same pixels, RNG states and ray counts either way. */
 enum rt_tuning_key { RT_TUNE_REGEN_THRESHOLD = 0, RT_TUNE_LEAF_MAX = 1, RT_TUNE_PERSISTENT_WAVES = 2,
                      RT_TUNE_SAH_TRAVERSAL = 3, RT_TUNE_LDS_PAD = 4, RT_TUNE_ADAPTIVE_ORDER = 5,
                      RT_TUNE_TEXEL_LAYOUT = 6, RT_TUNE_QUEUE_CHUNK = 7, RT_TUNE_QUEUE_STRIDE = 8,
@@ -623,7 +627,8 @@ enum rt_tuning_key { RT_TUNE_REGEN_THRESHOLD = 0, RT_TUNE_LEAF_MAX = 1, RT_TUNE_
                      RT_TUNE_QUEUE_MIN_CHUNK = 15, RT_TUNE_RIUS_TRIPS_PERSISTENT = 16, RT_TUNE_PREFETCH_STOP = 17,
                      RT_TUNE_PERSISTENT_GROUP = 18, RT_TUNE_GROUP_TAIL = 19, RT_TUNE_GROUP_ORDER = 20,
                      RT_TUNE_QUEUE_RESET = 21, RT_TUNE_GROUP_CHUNK = 22,
-                     RT_TUNE_GROUP_LINGER_US = 23, RT_TUNE_GROUP_WAVES = 24 };
+                     RT_TUNE_GROUP_LINGER_US = 23, RT_TUNE_GROUP_WAVES = 24,
+                     RT_TUNE_TILE_ENTRIES = 25 };
 int rt_set_tuning(int key, int value);
 
 /* ------------------------------------------------------------------------------------------------ */
@@ -711,6 +716,16 @@ typedef struct rt_host_tables_info {
 } rt_host_tables_info;
 int rt_build_host_tables(const rt_scene_desc* desc, float* nodes, float* prims, float* materials,
                          int32_t* prim_source, rt_host_tables_info* info);
+
+/* The v3 kernels' per-tile entry records, computed on the host by the classifier the device pre-pass runs: for tiles
+ * first_tile .. first_tile + num_tiles - 1 (8x8 tiles, row-major over ceil(width / 8) columns of the rank's local
+ * rows) of a frame of `desc` seen through `inputs`, four words each: eight 16-bit references, entry 0 = 0 "start at
+ * the root", else leaf references (~(first << 2 | count - 1) & 0xffff: primitives first .. first + count - 1 of the
+ * BVH-order table) that together hold every primitive a camera ray of the tile can hit, padded with 0x7fff.
+ * flags: RT_FLAG_FAITHFUL_GRID is honoured, other bits are ignored. */
+int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* inputs, uint32_t width, uint32_t height,
+                         const rt_tiling* tiling, uint32_t flags, uint32_t first_tile, uint32_t num_tiles,
+                         uint32_t* records);
 
 /* glibc random_r TYPE_3 restatement: rand() sequence after srand(seed) (RND macro, Math.cuh:12). */
 typedef struct rt_glibc_rand { int32_t r[34]; uint32_t idx; } rt_glibc_rand;

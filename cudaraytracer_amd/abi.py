@@ -26,7 +26,9 @@ RT_DENOISE_DEMODULATE = 1 << 0
 RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
 RT_TEMPORAL_RESET = 1 << 1
-ABI_VERSION = 10  # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host
+# RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host;
+# 11: RT_TUNE_CAMERA_RESOLVE
+ABI_VERSION = 11
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
 MOTION_IDENTITY = (0.0, 0.0, 0.0, 1.0)
@@ -49,7 +51,10 @@ RT_TUNE_GROUP_CHUNK = 22  # ... positions per chunk of the workgroup chunk queue
 RT_TUNE_GROUP_LINGER_US = 23  # ... a finished workgroup waits this long (us) for the grid's others before exiting
 RT_TUNE_GROUP_WAVES = 24  # ... waves per workgroup of the persistent flat kernel's group builds (4/8/12/16)
 RT_TUNE_TILE_ENTRIES = 25  # v3: camera rays start at their tile's candidate leaves (1) or at the root (0)
-RT_TUNE_GROUP_TAIL = 19  # ... permille of the tiles left to the per-wave queue behind the shares
+# v3: a shading pass resolves the next camera rays of its paths that missed by a scan of the tile's candidates (1;
+# 2..32: with that primitive cap) or leaves them to the leaf chain (0)
+RT_TUNE_CAMERA_RESOLVE = 26
+RT_TUNE_GROUP_TAIL = 19 # ... permille of the tiles left to the per-wave queue behind the shares
 
 STATUS = {
     0: "RT_OK",

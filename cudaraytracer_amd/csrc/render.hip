@@ -278,6 +278,9 @@ struct KParams {
     uint32_t group_chunk;            // ... positions per chunk (a multiple of 64)
     const uint4* tile_entries;       // v3 (16-bit references): per tile its entry record (rt_tile_entry.h), NULL = every
                                      // camera ray starts at the root (RT_TUNE_TILE_ENTRIES 0)
+    uint32_t camera_resolve;         // v3, with tile_entries: a shading pass ends its cleared misses first and resolves
+                                     // their next camera rays by a scan of the tile's record, where the record holds
+                                     // at most this many primitives (v3_resolve_camera; 0 = off, RT_TUNE_CAMERA_RESOLVE)
 };
 
 constexpr int kStackMax = 64;
@@ -875,6 +878,19 @@ __device__ __forceinline__ void camera_ray(PP P, const Camera& cam, R& rng, f3& 
     rd = normalize(sub(second, start));
 }
 
+// A path that ends in the sky (Kernel.cu:41-44): cur_attenuation * the background's blend by the ray's height.
+template <class PP>
+__device__ __forceinline__ f3 sky_contrib(PP P, const f3 rd, const f3 att) {
+    // rd.y / |rd|: below |rd.y| = 2^-100 the quotient's exact bits vanish in the + 1 (|q| < 2^-60)
+    const float len = length(rd);
+    float q;
+    if (in_rcp_range(len)) q = div_rn(rd.y, len, rcp_rn(len));
+    else q = rd.y / len;
+    const float tt = 0.5f * (q + 1.0f);
+    const f3 c = add(scale(1.0f - tt, mk(P->bg0[0], P->bg0[1], P->bg0[2])), scale(tt, mk(P->bg1[0], P->bg1[1], P->bg1[2])));
+    return mulv(att, c);
+}
+
 // One iteration of color()'s bounce loop after the closest-hit query (Kernel.cu:40-76): sky on a miss,
 // emission, or Scatter of the hit material.  Returns SHADE_ENDED when the path ended (contribution in
 // `contrib`, `emitted * cur_attenuation` or `cur_attenuation * sky`), SHADE_CONTINUE when it continues with
@@ -912,14 +928,7 @@ __device__ __forceinline__ int shade(PP P, const float4* __restrict__ prims, con
     }
     const bool specular = mtype == RT_METAL || mtype == RT_DIELECTRIC;
     if (hit < 0) {  // sky (Kernel.cu:41-44)
-        // rd.y / |rd|: below |rd.y| = 2^-100 the quotient's exact bits vanish in the + 1 (|q| < 2^-60)
-        const float len = length(rd);
-        float q;
-        if (in_rcp_range(len)) q = div_rn(rd.y, len, rcp_rn(len));
-        else q = rd.y / len;
-        const float tt = 0.5f * (q + 1.0f);
-        const f3 c = add(scale(1.0f - tt, mk(P->bg0[0], P->bg0[1], P->bg0[2])), scale(tt, mk(P->bg1[0], P->bg1[1], P->bg1[2])));
-        contrib = mulv(att, c);
+        contrib = sky_contrib(P, rd, att);
         return SHADE_ENDED;
     }
     if constexpr (!EXACT) {
@@ -1845,6 +1854,141 @@ __device__ __forceinline__ void v3_unpark(const uint32_t* park, R& rng, f3& col,
 }
 
 
+// The pre-step of a v3 shading pass (P.camera_resolve; full tiles with a record, 16-bit references): a MODE_SHADE lane
+// whose ray missed, where bvh_clear clears the miss, ends its path here — the sky term, add_sample and the next
+// sample's camera ray, as shade()'s miss and v3_next_sample do them; the sky draws no random number, so the RNG order
+// is the same — and that camera ray is resolved at once by a scan of the tile's record: the record's references in
+// order, each primitive read with scalar loads (the tile, so the record and every address, is wave-uniform) and tested
+// as v3_traverse's leaf loop tests it.  The lane stays in MODE_SHADE with the camera ray's (hit, tag, t_best), att = 1
+// and depth = 0, and the pass's one shade() call serves it together with the bounce hits: it enters the next traversal
+// call with a bounce ray, not with a leaf chain to hold through the node phase.  Any other path end (absorption,
+// the depth limit, an emitter, a camera ray that missed) takes v3_next_sample and the leaf chain as before, and so does
+// every lane of a tile whose record says "root" or holds more than P.camera_resolve primitives.
+// The tests below are the leaf loop's — the same expressions, acceptance rules, kTieBit rules and tag — as a second
+// copy, so that the leaf loop's code stays as it is: keep the two in step.  Exactness as for
+// v3_start_camera_trace: the candidates hold every primitive whose test can accept a ray of the beam, ties are flagged
+// in any order, and bvh_clear / ref_trace_wave read the hit record and the reference tables only.
+// The lane's parked path state is taken from LDS and put back here, for the lanes of the pre-step alone and ahead of
+// the scan, which then runs on the ray and its own few values: held in registers from the pass's unpark through the
+// scan to shade(), the state cost the 8-waves-per-SIMD builds 28 spilled VGPRs.
+template <bool COUNT_TESTS, class R, bool COMPACT>
+__device__ __forceinline__ void v3_resolve_camera(const uint32_t x, const uint32_t g, const uint32_t tile, uint32_t* const park,
+                                                  f3& ro, f3& rd, Cursor& c, Counts& cnt) {
+    typedef const __attribute__((address_space(4))) uint32_t ConstWord;
+    typedef const __attribute__((address_space(4))) float ConstFloat;
+    constexpr bool EXACT = RT_BVH_EXACT != 0;
+    KParamsC* q = kparams_reload();
+    ConstWord* const r = (ConstWord*)q->tile_entries + 4u * (size_t)__builtin_amdgcn_readfirstlane(tile);  // (one s_load_dwordx4)
+    const uint32_t rx = r[0], ry = r[1], rz = r[2], rw = r[3];
+    if ((rx & 0xffffu) == kTileEntryRoot) return;
+    // eight 16-bit references from the front, the sentinel shifted in behind them
+    uint64_t lo = (uint64_t)rx | (uint64_t)ry << 32, hi = (uint64_t)rz | (uint64_t)rw << 32;
+    {
+        uint32_t total = 0u;  // the record's primitives: a reference's low two bits hold ~(count - 1)
+        const uint32_t w[4] = {rx, ry, rz, rw};
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            const uint32_t e = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+            total += e != kTileEntryNone ? ((e ^ 0xffffu) & 3u) + 1u : 0u;
+        }
+        if (total > q->camera_resolve) return;
+    }
+    const bool verified = c.hit == kVerifiedMiss;
+    bool ends = c.mode == MODE_SHADE && (c.hit < 0 || verified);
+    if (RT_BVH_EXACT != 0 && RT_BVH_EXACT != 2 && RT_BVH_EXACT != 3)  // (bvh_clear's rule for a miss)
+        ends = ends && (verified || !(q->bvh_has_rects && bvh_odd_ray(ro, rd)));
+    if (!ends) return;
+    {
+        R rng;
+        f3 col, att;
+        uint32_t sample, depth, rays;
+        v3_unpark<COMPACT, true>(park, rng, col, att, sample, depth, rays);
+        col = add_sample(rng, col, sky_contrib(q, rd, att));
+        const Camera cam = lane_camera(q, x, g);
+        bool fresh = false;
+        while (++sample < q->spp) {  // (as v3_next_sample)
+            camera_ray(q, cam, rng, ro, rd, sample);
+            if (q->max_depth > 0) {
+                fresh = true;
+                rays++;  // (as v3_start_trace)
+                break;
+            }
+            col = add_sample(rng, col, mk(0.0f, 0.0f, 0.0f));  // exceeded recursion (Kernel.cu:79)
+        }
+        v3_park<COMPACT, true>(park, rng, col, mk(1.0f, 1.0f, 1.0f), sample, 0u, rays);
+        if (!fresh) {
+            c.mode = MODE_DONE;
+            return;
+        }
+    }
+    int hit = -1;
+    uint32_t tag = c.tag;
+    float t_best = FLT_MAX;
+    const float a_dd = dot(rd, rd);
+    const bool fast_div = a_dd >= 0x1p-40f && a_dd <= 0x1p40f;
+    const float inv_a = rcp_rn(a_dd);  // used only when fast_div
+    ConstFloat* const pbase = (ConstFloat*)q->prims;
+    for (uint32_t e = (uint32_t)lo & 0xffffu; e != kTileEntryNone; e = (uint32_t)lo & 0xffffu) {
+        lo = lo >> 16 | hi << 48;
+        hi = hi >> 16 | (uint64_t)kTileEntryNone << 48;
+        const uint32_t l = e ^ 0xffffu;
+        const uint32_t first = l >> 2, last = first + (l & 3u);
+        for (uint32_t i = first; i <= last; i++) {
+            ConstFloat* const pp = pbase + 8u * (size_t)i;
+            const float4 p0 = make_float4(pp[0], pp[1], pp[2], pp[3]);
+            const float4 p1 = make_float4(pp[4], pp[5], pp[6], pp[7]);
+            const uint32_t type = __float_as_uint(p1.w) & 15u;
+            if (COUNT_TESTS) {
+                cnt.prims++;
+                cnt.rects += type != RT_SPHERE ? 1u : 0u;
+            }
+            if (type == RT_SPHERE) {  // Sphere::Hit (Hittable.cuh:80-110)
+                const f3 oc = sub(ro, xyz(p0));
+                const float b = dot(oc, rd);
+                const float cc = dot(oc, oc) - p1.x;
+                const float disc = b * b - a_dd * cc;
+                if (disc > 0) {
+                    const float sq = sqrt_fast(disc);
+                    float t = fast_div ? div_rn(-b - sq, a_dd, inv_a) : (-b - sq) / a_dd;
+                    if (t < t_best && t > kTmin) {
+                        t_best = t;
+                        hit = (int)i;
+                        tag = __float_as_uint(p1.w);
+                    } else {
+                        const bool tied = EXACT && t == t_best;  // (bvh_clear: a tie at the closest hit so far)
+                        t = fast_div ? div_rn(-b + sq, a_dd, inv_a) : (-b + sq) / a_dd;
+                        if (t < t_best && t > kTmin) {
+                            t_best = t;
+                            hit = (int)i;
+                            tag = __float_as_uint(p1.w);
+                        } else if (EXACT && (tied || t == t_best)) {
+                            hit |= kTieBit;
+                        }
+                    }
+                }
+            } else {  // *Rect::Hit
+                const float ok = type == RT_XYRECT ? ro.z : (type == RT_XZRECT ? ro.y : ro.x);
+                const float dk = type == RT_XYRECT ? rd.z : (type == RT_XZRECT ? rd.y : rd.x);
+                const float t = (p0.x - ok) * rcp_ieee(dk);
+                if (!(t < kTmin || t > t_best)) {
+                    const float oa = type == RT_YZRECT ? ro.y : ro.x, da = type == RT_YZRECT ? rd.y : rd.x;
+                    const float ob = type == RT_XYRECT ? ro.y : ro.z, db = type == RT_XYRECT ? rd.y : rd.z;
+                    const float xx = oa + t * da;
+                    const float yy = ob + t * db;
+                    if (!(xx < p0.y || xx > p0.z || yy < p0.w || yy > p1.x)) {
+                        hit = EXACT && t == t_best ? (int)i | kTieBit : (int)i;  // (a rectangle re-accepts an equal t)
+                        t_best = t;
+                        tag = __float_as_uint(p1.w);
+                    }
+                }
+            }
+        }
+    }
+    c.hit = hit;
+    c.tag = tag;
+    c.t_best = t_best;
+}
+
 // Constant-address-space views of the read-only scene buffers: loads from them at wave-uniform indices become
 // scalar loads (s_load_dword*) whose results feed VALU instructions as SGPR operands.
 typedef const __attribute__((address_space(4))) float ConstF32;
@@ -2293,6 +2437,12 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
         const uint64_t t_b = COUNT_TESTS ? __builtin_amdgcn_s_memtime() : 0;
         if (COUNT_TESTS) cnt.ctrav += t_b - t_a;
         for (;;) {  // the shading pass, and once more for lanes whose hit the reference traversal replayed
+            // (not in the sample-items builds: a full tile of theirs hands out items, and their other tiles have no
+            // record; launch-uniform: a launch without a table pays this branch only)
+            if constexpr (!WIDE && !kItemsBuild) {
+                if (kparams_reload()->camera_resolve != 0u)
+                    v3_resolve_camera<COUNT_TESTS, R, COMPACT>(x, g, tile, park, ro, rd, c, cnt);
+            }
             if (c.mode == MODE_SHADE) {
                 R rng;
                 f3 col, att;
@@ -4009,6 +4159,13 @@ int acquire_plan(const PlanKey& key, hipStream_t s, std::shared_ptr<TilePlan>* o
 // RT_TUNE_TILE_ENTRIES: 1 (default) = the v3 kernels start a full tile's camera rays at the tile's candidate leaves
 // (rt_tile_entry.h; 16-bit-reference scenes, band_rows a multiple of 8), 0 = every ray starts at the root (A/B, tests)
 thread_local int g_tile_entries = 1;
+// RT_TUNE_CAMERA_RESOLVE: 1 (default) = with the entry records, a v3 shading pass ends its cleared misses ahead of
+// shade() and resolves their next camera rays by a scan of the tile's record (v3_resolve_camera), for records of at
+// most kCameraResolveCap primitives; 2..32 = the same with that cap (A/B, tests); 0 = off: every camera ray takes the
+// leaf chain (the parent's behaviour)
+thread_local int g_camera_resolve = 1;
+constexpr uint32_t kCameraResolveCap = 8;
+constexpr int kCameraResolveMax = 32;  // a record's eight references hold at most four primitives each
 
 // Per (device, stream, tile grid): the tiles' entry records and what they were filled for.  The pre-pass runs again
 // only when the scene, the camera terms, the frame shape or the band layout differ from the launch that filled the
@@ -4635,6 +4792,15 @@ int rt_set_tuning(int key, int value) {
         g_tile_entries = value;
         return prev;
     }
+    if (key == RT_TUNE_CAMERA_RESOLVE) {
+        if (value < 0 || value > kCameraResolveMax) {
+            set_error("rt_set_tuning: camera resolve must be 0, 1 or a primitive cap in [2, 32]");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        int prev = g_camera_resolve;
+        g_camera_resolve = value;
+        return prev;
+    }
     set_error("rt_set_tuning: unknown key");
     return RT_ERR_INVALID_ARGUMENT;
 }
@@ -4964,6 +5130,7 @@ int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) 
             entries->frame = F;
         }
         P.tile_entries = (const uint4*)entries->rec;
+        P.camera_resolve = g_camera_resolve == 1 ? kCameraResolveCap : (uint32_t)g_camera_resolve;
     }
     if (trial) (void)hipEventRecord(trial->ev[trial_slot], s);
     (void)hipGetLastError();

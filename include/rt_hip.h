@@ -183,8 +183,8 @@ const char* rt_version(void);
 /* Version of this C ABI (structure layouts, counter words, entry points); a caller built against an older header
  * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
  * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal.  9: rt_scene_motion, rt_temporal_dynamic,
- * rt_scene_edit. */
-#define RT_ABI_VERSION 10
+ * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE. */
+#define RT_ABI_VERSION 11
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -618,7 +618,12 @@ int rt_last_variant(void);
  *   RT_TUNE_TILE_ENTRIES: 1 (default) = the v3 kernels (variants 2, 3) start the camera rays of a full 8x8 tile at the
  *   BVH leaves the tile's beam can touch, from a per-tile table a pre-pass fills when the scene, the camera, the frame
  *   shape or the band layout changed (rt_tile_entries_host; scenes with 16-bit references and band_rows a multiple of
- *   8); 0 = every ray starts at the root.  Same pixels, RNG states and ray counts either way. */
+ *   8); 0 = every ray starts at the root.  Same pixels, RNG states and ray counts either way.
+ *   RT_TUNE_CAMERA_RESOLVE: 1 (default) = where RT_TUNE_TILE_ENTRIES applies, a v3 shading pass first ends the paths
+ *   whose ray missed (the sky term) and resolves their next camera rays by a wave-uniform scan of the tile's candidate
+ *   primitives, so those rays are shaded in the same pass and never enter a traversal call; tiles whose record holds
+ *   more than 8 primitives keep the leaf chain.  2..32 = the same with that primitive cap; 0 = off.  Same pixels, RNG
+ *   states and ray counts for every value. */
 enum rt_tuning_key { RT_TUNE_REGEN_THRESHOLD = 0, RT_TUNE_LEAF_MAX = 1, RT_TUNE_PERSISTENT_WAVES = 2,
                      RT_TUNE_SAH_TRAVERSAL = 3, RT_TUNE_LDS_PAD = 4, RT_TUNE_ADAPTIVE_ORDER = 5,
                      RT_TUNE_TEXEL_LAYOUT = 6, RT_TUNE_QUEUE_CHUNK = 7, RT_TUNE_QUEUE_STRIDE = 8,
@@ -628,7 +633,7 @@ enum rt_tuning_key { RT_TUNE_REGEN_THRESHOLD = 0, RT_TUNE_LEAF_MAX = 1, RT_TUNE_
                      RT_TUNE_PERSISTENT_GROUP = 18, RT_TUNE_GROUP_TAIL = 19, RT_TUNE_GROUP_ORDER = 20,
                      RT_TUNE_QUEUE_RESET = 21, RT_TUNE_GROUP_CHUNK = 22,
                      RT_TUNE_GROUP_LINGER_US = 23, RT_TUNE_GROUP_WAVES = 24,
-                     RT_TUNE_TILE_ENTRIES = 25 };
+                     RT_TUNE_TILE_ENTRIES = 25, RT_TUNE_CAMERA_RESOLVE = 26 };
 int rt_set_tuning(int key, int value);
 
 /* ------------------------------------------------------------------------------------------------ */

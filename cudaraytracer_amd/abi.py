@@ -27,8 +27,8 @@ RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
 RT_TEMPORAL_RESET = 1 << 1
 # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host;
-# 11: RT_TUNE_CAMERA_RESOLVE
-ABI_VERSION = 11
+# 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP
+ABI_VERSION = 12
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
 MOTION_IDENTITY = (0.0, 0.0, 0.0, 1.0)
@@ -54,6 +54,8 @@ RT_TUNE_TILE_ENTRIES = 25  # v3: camera rays start at their tile's candidate lea
 # v3: a shading pass resolves the next camera rays of its paths that missed by a scan of the tile's candidates (1;
 # 2..32: with that primitive cap) or leaves them to the leaf chain (0)
 RT_TUNE_CAMERA_RESOLVE = 26
+# v3: where that scan applies, every path end and the pixel's first camera ray go through it (1) or only misses do (0)
+RT_TUNE_PATH_END_STEP = 27
 RT_TUNE_GROUP_TAIL = 19 # ... permille of the tiles left to the per-wave queue behind the shares
 
 STATUS = {

@@ -281,6 +281,9 @@ struct KParams {
     uint32_t camera_resolve;         // v3, with tile_entries: a shading pass ends its cleared misses first and resolves
                                      // their next camera rays by a scan of the tile's record, where the record holds
                                      // at most this many primitives (v3_resolve_camera; 0 = off, RT_TUNE_CAMERA_RESOLVE)
+    uint32_t path_end_step;          // v3, with camera_resolve: in a wave whose record the pre-step scans, every path end
+                                     // (and the pixel's first camera ray) goes through the pre-step: the lane waits in
+                                     // MODE_ENDED with its contribution parked (0 = only cleared misses, RT_TUNE_PATH_END_STEP)
 };
 
 constexpr int kStackMax = 64;
@@ -1450,6 +1453,8 @@ constexpr int kSentinel = 0x7fffffff;  // traversal finished (internal node ids 
 enum LaneMode { MODE_TRAV = 0, MODE_SHADE = 1, MODE_DONE = 2 };
 constexpr int MODE_NEED = 3;  // v4 / persistent flat: the lane waits for a pixel; v3 sample items: for a sample
 constexpr int MODE_REPLAY = 4;  // v3 / v4: the closest hit replays the reference traversal before shading (bvh_replay)
+constexpr int MODE_ENDED = 5;  // v3 (P.path_end_step): the path has ended, its contribution is parked in the attenuation
+                               // words; the next shading pass's pre-step adds it and resolves the next camera ray
 
 template <bool COUNT_TESTS, int BLOCK = 64>
 __global__ __launch_bounds__(BLOCK) void render_kernel_v2(const KParams P) {
@@ -1854,6 +1859,24 @@ __device__ __forceinline__ void v3_unpark(const uint32_t* park, R& rng, f3& col,
 }
 
 
+// The tile's record as the pre-step scans it: eight 16-bit references from the front in (lo, hi), the sentinel shifted
+// in behind them.  False (wave-uniform) for a "root" record and for one of more than q->camera_resolve primitives.
+__device__ __forceinline__ bool v3_scan_record(KParamsC* q, const uint32_t tile, uint64_t& lo, uint64_t& hi) {
+    typedef const __attribute__((address_space(4))) uint32_t ConstWord;
+    ConstWord* const r = (ConstWord*)q->tile_entries + 4u * (size_t)__builtin_amdgcn_readfirstlane(tile);  // (one s_load_dwordx4)
+    const uint32_t rx = r[0], ry = r[1], rz = r[2], rw = r[3];
+    lo = (uint64_t)rx | (uint64_t)ry << 32, hi = (uint64_t)rz | (uint64_t)rw << 32;
+    if ((rx & 0xffffu) == kTileEntryRoot) return false;
+    uint32_t total = 0u;  // the record's primitives: a reference's low two bits hold ~(count - 1)
+    const uint32_t w[4] = {rx, ry, rz, rw};
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        const uint32_t e = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
+        total += e != kTileEntryNone ? ((e ^ 0xffffu) & 3u) + 1u : 0u;
+    }
+    return total <= q->camera_resolve;
+}
+
 // The pre-step of a v3 shading pass (P.camera_resolve; full tiles with a record, 16-bit references): a MODE_SHADE lane
 // whose ray missed, where bvh_clear clears the miss, ends its path here — the sky term, add_sample and the next
 // sample's camera ray, as shade()'s miss and v3_next_sample do them; the sky draws no random number, so the RNG order
@@ -1861,9 +1884,9 @@ __device__ __forceinline__ void v3_unpark(const uint32_t* park, R& rng, f3& col,
 // order, each primitive read with scalar loads (the tile, so the record and every address, is wave-uniform) and tested
 // as v3_traverse's leaf loop tests it.  The lane stays in MODE_SHADE with the camera ray's (hit, tag, t_best), att = 1
 // and depth = 0, and the pass's one shade() call serves it together with the bounce hits: it enters the next traversal
-// call with a bounce ray, not with a leaf chain to hold through the node phase.  Any other path end (absorption,
-// the depth limit, an emitter, a camera ray that missed) takes v3_next_sample and the leaf chain as before, and so does
-// every lane of a tile whose record says "root" or holds more than P.camera_resolve primitives.
+// call with a bounce ray, not with a leaf chain to hold through the node phase.  Without P.path_end_step any other path
+// end (absorption, the depth limit, an emitter, a camera ray that missed) takes v3_next_sample and the leaf chain, and
+// so does every lane of a tile whose record says "root" or holds more than P.camera_resolve primitives.
 // The tests below are the leaf loop's — the same expressions, acceptance rules, kTieBit rules and tag — as a second
 // copy, so that the leaf loop's code stays as it is: keep the two in step.  Exactness as for
 // v3_start_camera_trace: the candidates hold every primitive whose test can accept a ray of the beam, ties are flagged
@@ -1871,42 +1894,38 @@ __device__ __forceinline__ void v3_unpark(const uint32_t* park, R& rng, f3& col,
 // The lane's parked path state is taken from LDS and put back here, for the lanes of the pre-step alone and ahead of
 // the scan, which then runs on the ray and its own few values: held in registers from the pass's unpark through the
 // scan to shade(), the state cost the 8-waves-per-SIMD builds 28 spilled VGPRs.
+// With P.path_end_step every other path end of a wave whose record is scanned comes here as well: shade()'s caller
+// leaves the lane in MODE_ENDED with the path's contribution in the parked attenuation words (dead once a path has
+// ended, reset to 1 here), and this step adds it where the sky term is added for a cleared miss; the pixel's first
+// camera ray is the "end" of a path with contribution 0 and sample -1.  No lane of the wave then holds a camera ray's
+// leaf chain through a traversal call, and v3_next_sample does not execute.  Per lane the RNG draws and add_sample
+// calls keep their order.
 template <bool COUNT_TESTS, class R, bool COMPACT>
 __device__ __forceinline__ void v3_resolve_camera(const uint32_t x, const uint32_t g, const uint32_t tile, uint32_t* const park,
                                                   f3& ro, f3& rd, Cursor& c, Counts& cnt) {
-    typedef const __attribute__((address_space(4))) uint32_t ConstWord;
     typedef const __attribute__((address_space(4))) float ConstFloat;
     constexpr bool EXACT = RT_BVH_EXACT != 0;
     KParamsC* q = kparams_reload();
-    ConstWord* const r = (ConstWord*)q->tile_entries + 4u * (size_t)__builtin_amdgcn_readfirstlane(tile);  // (one s_load_dwordx4)
-    const uint32_t rx = r[0], ry = r[1], rz = r[2], rw = r[3];
-    if ((rx & 0xffffu) == kTileEntryRoot) return;
-    // eight 16-bit references from the front, the sentinel shifted in behind them
-    uint64_t lo = (uint64_t)rx | (uint64_t)ry << 32, hi = (uint64_t)rz | (uint64_t)rw << 32;
-    {
-        uint32_t total = 0u;  // the record's primitives: a reference's low two bits hold ~(count - 1)
-        const uint32_t w[4] = {rx, ry, rz, rw};
-#pragma unroll
-        for (int k = 0; k < 8; k++) {
-            const uint32_t e = (w[k >> 1] >> (16 * (k & 1))) & 0xffffu;
-            total += e != kTileEntryNone ? ((e ^ 0xffffu) & 3u) + 1u : 0u;
-        }
-        if (total > q->camera_resolve) return;
-    }
+    uint64_t lo, hi;
+    if (!v3_scan_record(q, tile, lo, hi)) return;
     const bool verified = c.hit == kVerifiedMiss;
     bool ends = c.mode == MODE_SHADE && (c.hit < 0 || verified);
     if (RT_BVH_EXACT != 0 && RT_BVH_EXACT != 2 && RT_BVH_EXACT != 3)  // (bvh_clear's rule for a miss)
         ends = ends && (verified || !(q->bvh_has_rects && bvh_odd_ray(ro, rd)));
+    const bool parked_end = c.mode == MODE_ENDED;  // (only with q->path_end_step)
+    ends = ends || parked_end;
     if (!ends) return;
     {
         R rng;
         f3 col, att;
         uint32_t sample, depth, rays;
         v3_unpark<COMPACT, true>(park, rng, col, att, sample, depth, rays);
-        col = add_sample(rng, col, sky_contrib(q, rd, att));
+        const f3 sky = sky_contrib(q, rd, att);
+        col = add_sample(rng, col, parked_end ? att : sky);
         const Camera cam = lane_camera(q, x, g);
         bool fresh = false;
-        while (++sample < q->spp) {  // (as v3_next_sample)
+        // (compact parking holds the first ray's sample -1 as 13 set bits; a sample index is below 8191 there)
+        while ((sample = COMPACT ? (sample + 1u) & 0x1fffu : sample + 1u) < q->spp) {  // (as v3_next_sample)
             camera_ray(q, cam, rng, ro, rd, sample);
             if (q->max_depth > 0) {
                 fresh = true;
@@ -1921,6 +1940,7 @@ __device__ __forceinline__ void v3_resolve_camera(const uint32_t x, const uint32
             return;
         }
     }
+    c.mode = MODE_SHADE;
     int hit = -1;
     uint32_t tag = c.tag;
     float t_best = FLT_MAX;
@@ -2402,6 +2422,15 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
     const auto item_sum = [&](uint32_t p, int ch) -> unsigned long long* {
         return (unsigned long long*)(wl + (ch < 2 ? 64u + 2u * ((uint32_t)ch * 64u + p) : 384u + 2u * p));
     };
+    // P.path_end_step, a wave whose record the pre-step scans (wave-uniform, launch-constant): its path ends wait in
+    // MODE_ENDED for the next pass's pre-step.  (camera_resolve != 0 says that there is a table, spp > 0 and
+    // max_depth > 0.)
+    bool pend = false;
+    if constexpr (!WIDE && !kItemsBuild) {
+        KParamsC* q = kparams_reload();
+        uint64_t lo, hi;
+        if (q->camera_resolve != 0u && q->path_end_step != 0u) pend = v3_scan_record(q, tile, lo, hi);
+    }
     {  // first camera ray of the pixel
         uint32_t* st = state_at(P, pix);
         R rng = begin_rng<R>(st, P.state_stride, g * P.width + x);  // global pixel index (Kernel.cu:119)
@@ -2409,7 +2438,13 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
         // (sample = -1: v3_next_sample starts sample 0; with spp = 0 it stays 0, so compact parking's packed
         // sample field cannot spill into the ray count)
         uint32_t sample = P.spp > 0 ? (uint32_t)-1 : 0u, depth = 0, rays = 0;
-        if (P.spp > 0) v3_next_sample<WIDE>(P, x, g, mk(0.0f, 0.0f, 0.0f), rng, col, att, sample, depth, ro, rd, c, rays, tile, stk);
+        // (pend: the first ray is the pre-step's too — the lane waits with contribution 0 and sample -1, 13 set bits
+        // in compact parking's field)
+        if (pend) {
+            att = mk(0.0f, 0.0f, 0.0f);
+            if (COMPACT) sample = 0x1fffu;
+            c.mode = MODE_ENDED;
+        } else if (P.spp > 0) v3_next_sample<WIDE>(P, x, g, mk(0.0f, 0.0f, 0.0f), rng, col, att, sample, depth, ro, rd, c, rays, tile, stk);
         v3_park<COMPACT>(park, rng, col, att, items ? lane : sample, depth, rays);  // (col + 0 = +0 above)
         if (kItemsBuild && items) {  // (after the park above, which wrote colour words)
             park[1 * 64] = park[2 * 64] = park[3 * 64] = park[4 * 64] = 0u;
@@ -2474,6 +2509,9 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
                     park[8 * 64] += rays;
                     rays = 0u;
                     c.mode = MODE_NEED;
+                } else if (ended && pend) {  // the contribution waits in the attenuation words for the next pre-step
+                    att = contrib;
+                    c.mode = MODE_ENDED;
                 } else if (ended) {  // the colour sum stays parked until a path ends (3 fewer VGPRs live through shade())
                     col = mk(__uint_as_float(park[(PK_COL + 0) * 64]), __uint_as_float(park[(PK_COL + 1) * 64]),
                              __uint_as_float(park[(PK_COL + 2) * 64]));
@@ -4166,6 +4204,10 @@ thread_local int g_tile_entries = 1;
 thread_local int g_camera_resolve = 1;
 constexpr uint32_t kCameraResolveCap = 8;
 constexpr int kCameraResolveMax = 32;  // a record's eight references hold at most four primitives each
+// RT_TUNE_PATH_END_STEP: 1 (default) = where the pre-step scans a wave's record, every path end of the wave (absorption,
+// the depth limit, an emitter, a camera ray that missed) and the pixel's first camera ray go through the pre-step too:
+// no lane holds a camera ray's leaf chain through a traversal call; 0 = only cleared misses do (A/B, tests)
+thread_local int g_path_end_step = 1;
 
 // Per (device, stream, tile grid): the tiles' entry records and what they were filled for.  The pre-pass runs again
 // only when the scene, the camera terms, the frame shape or the band layout differ from the launch that filled the
@@ -4801,6 +4843,15 @@ int rt_set_tuning(int key, int value) {
         g_camera_resolve = value;
         return prev;
     }
+    if (key == RT_TUNE_PATH_END_STEP) {
+        if (value < 0 || value > 1) {
+            set_error("rt_set_tuning: path end step must be 0 or 1");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        int prev = g_path_end_step;
+        g_path_end_step = value;
+        return prev;
+    }
     set_error("rt_set_tuning: unknown key");
     return RT_ERR_INVALID_ARGUMENT;
 }
@@ -5131,6 +5182,7 @@ int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) 
         }
         P.tile_entries = (const uint4*)entries->rec;
         P.camera_resolve = g_camera_resolve == 1 ? kCameraResolveCap : (uint32_t)g_camera_resolve;
+        P.path_end_step = (uint32_t)g_path_end_step;
     }
     if (trial) (void)hipEventRecord(trial->ev[trial_slot], s);
     (void)hipGetLastError();

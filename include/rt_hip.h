@@ -183,8 +183,8 @@ const char* rt_version(void);
 /* Version of this C ABI (structure layouts, counter words, entry points); a caller built against an older header
  * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
  * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal.  9: rt_scene_motion, rt_temporal_dynamic,
- * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE. */
-#define RT_ABI_VERSION 11
+ * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE.  12: RT_TUNE_PATH_END_STEP. */
+#define RT_ABI_VERSION 12
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -623,7 +623,11 @@ int rt_last_variant(void);
  *   whose ray missed (the sky term) and resolves their next camera rays by a wave-uniform scan of the tile's candidate
  *   primitives, so those rays are shaded in the same pass and never enter a traversal call; tiles whose record holds
  *   more than 8 primitives keep the leaf chain.  2..32 = the same with that primitive cap; 0 = off.  Same pixels, RNG
- *   states and ray counts for every value. */
+ *   states and ray counts for every value.
+ *   RT_TUNE_PATH_END_STEP: 1 (default) = in a wave whose tile RT_TUNE_CAMERA_RESOLVE scans, every other path end
+ *   (an absorbed scatter, the depth limit, an emitter, a camera ray that missed) and the pixel's first camera ray take
+ *   that step as well: the lane waits one pass with its contribution parked, and no camera ray of the wave enters a
+ *   traversal call; 0 = only the paths whose ray missed do.  Same pixels, RNG states and ray counts either way. */
 enum rt_tuning_key { RT_TUNE_REGEN_THRESHOLD = 0, RT_TUNE_LEAF_MAX = 1, RT_TUNE_PERSISTENT_WAVES = 2,
                      RT_TUNE_SAH_TRAVERSAL = 3, RT_TUNE_LDS_PAD = 4, RT_TUNE_ADAPTIVE_ORDER = 5,
                      RT_TUNE_TEXEL_LAYOUT = 6, RT_TUNE_QUEUE_CHUNK = 7, RT_TUNE_QUEUE_STRIDE = 8,
@@ -633,7 +637,7 @@ enum rt_tuning_key { RT_TUNE_REGEN_THRESHOLD = 0, RT_TUNE_LEAF_MAX = 1, RT_TUNE_
                      RT_TUNE_PERSISTENT_GROUP = 18, RT_TUNE_GROUP_TAIL = 19, RT_TUNE_GROUP_ORDER = 20,
                      RT_TUNE_QUEUE_RESET = 21, RT_TUNE_GROUP_CHUNK = 22,
                      RT_TUNE_GROUP_LINGER_US = 23, RT_TUNE_GROUP_WAVES = 24,
-                     RT_TUNE_TILE_ENTRIES = 25, RT_TUNE_CAMERA_RESOLVE = 26 };
+                     RT_TUNE_TILE_ENTRIES = 25, RT_TUNE_CAMERA_RESOLVE = 26, RT_TUNE_PATH_END_STEP = 27 };
 int rt_set_tuning(int key, int value);
 
 /* ------------------------------------------------------------------------------------------------ */

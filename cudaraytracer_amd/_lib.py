@@ -51,6 +51,9 @@ EXPORTED = [
     "rt_denoise_scratch_bytes",
     "rt_temporal",
     "rt_temporal_dynamic",
+    "rt_temporal_moments",
+    "rt_denoise_variance",
+    "rt_denoise_variance_scratch_bytes",
     "rt_scene_motion",
     "rt_scene_edit",
     "rt_last_kernel_ms",
@@ -112,6 +115,10 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_denoise_scratch_bytes.restype = C.c_uint64
     lib.rt_temporal.argtypes = [P(abi.TemporalArgs), vp]
     lib.rt_temporal_dynamic.argtypes = [P(abi.TemporalArgs), vp, C.c_uint32, vp]
+    lib.rt_temporal_moments.argtypes = [P(abi.TemporalArgs), vp, C.c_uint32, vp, vp, vp]
+    lib.rt_denoise_variance.argtypes = [P(abi.DenoiseVarianceArgs), vp]
+    lib.rt_denoise_variance_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
+    lib.rt_denoise_variance_scratch_bytes.restype = C.c_uint64
     lib.rt_scene_motion.argtypes = [P(abi.HittableDesc), P(abi.HittableDesc), C.c_uint32, P(C.c_float)]
     lib.rt_scene_edit.argtypes = [vp, P(abi.HittableDesc), C.c_uint32, P(vp)]
     lib.rt_last_kernel_ms.restype = C.c_float

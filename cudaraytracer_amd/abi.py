@@ -27,8 +27,9 @@ RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
 RT_TEMPORAL_RESET = 1 << 1
 # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host;
-# 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP
-ABI_VERSION = 12
+# 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP; 13: rt_temporal_moments, rt_denoise_variance,
+# rt_denoise_variance_scratch_bytes
+ABI_VERSION = 13
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
 MOTION_IDENTITY = (0.0, 0.0, 0.0, 1.0)
@@ -206,6 +207,30 @@ class DenoiseArgs(C.Structure):
         ("sigma_n", C.c_float),
         ("sigma_z", C.c_float),
         ("reserved", C.c_uint32),
+        ("tiling", Tiling),
+    ]
+
+
+class DenoiseVarianceArgs(C.Structure):
+    """rt_denoise_variance_args, 112 bytes."""
+
+    _fields_ = [
+        ("color", C.c_void_p),
+        ("moments", C.c_void_p),
+        ("normal_depth", C.c_void_p),
+        ("prim_id", C.c_void_p),
+        ("out_color", C.c_void_p),
+        ("pos", C.c_void_p),
+        ("scratch", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("iterations", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("sigma_l", C.c_float),
+        ("sigma_n", C.c_float),
+        ("sigma_z", C.c_float),
+        ("min_history", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
         ("tiling", Tiling),
     ]
 

@@ -653,6 +653,50 @@ int rt_temporal_dynamic(const rt_temporal_args* a, const float* prim_motion, uin
     return launch_temporal_dynamic(P, prim_motion, num_prims, stream);
 }
 
+int rt_temporal_moments(const rt_temporal_args* a, const float* prim_motion, uint32_t num_prims, const float* prev_moments,
+                        float* moments, rt_stream stream) {
+    TemporalParams P;
+    uint64_t n = 0;
+    const int rc = temporal_params("rt_temporal_moments", a, &P, &n);
+    if (rc) return rc;
+    const auto bad = [](const char* msg) {
+        set_error(std::string("rt_temporal_moments: ") + msg);
+        return (int)RT_ERR_INVALID_ARGUMENT;
+    };
+    const bool reset = (a->flags & RT_TEMPORAL_RESET) != 0;
+    const bool dynamic = prim_motion != nullptr;  // NULL: rt_temporal's semantics, else rt_temporal_dynamic's
+    if (!dynamic && num_prims != 0) return bad("NULL prim_motion with num_prims > 0");
+    if (!moments) return bad("NULL moments (the output plane)");
+    if (!reset && !prev_moments) return bad("NULL prev_moments without RT_TEMPORAL_RESET");
+    const uint64_t table_bytes = (uint64_t)num_prims * 16u;
+    const void* outs[3] = {a->history, a->motion, a->pos};
+    const uint64_t out_bytes[3] = {n * 16u, n * 8u, n * 4u};
+    if (dynamic && !reset) {  // (with RT_TEMPORAL_RESET the table is never read)
+        if ((uintptr_t)prim_motion % 16u) return bad("prim_motion must be 16-byte aligned (float4 entries)");
+        for (int o = 0; o < 3; o++)
+            if (overlaps(outs[o], out_bytes[o], prim_motion, table_bytes)) return bad("an output overlaps the prim_motion table");
+    }
+    // the moments plane against everything the launch reads or writes
+    const void* ins[3] = {a->color, a->normal_depth, a->prim_id};
+    const uint64_t in_bytes[3] = {n * 16u, n * 16u, n * 4u};
+    for (int i = 0; i < 3; i++)
+        if (overlaps(moments, n * 8u, ins[i], in_bytes[i])) return bad("moments overlaps an input plane");
+    for (int o = 0; o < 3; o++)
+        if (overlaps(moments, n * 8u, outs[o], out_bytes[o])) return bad("moments overlaps another output");
+    if (!reset) {
+        const void* prevs[4] = {a->prev_history, a->prev_normal_depth, a->prev_prim_id, prev_moments};
+        const uint64_t prev_bytes[4] = {n * 16u, n * 16u, n * 4u, n * 8u};
+        for (int i = 0; i < 4; i++)
+            if (overlaps(moments, n * 8u, prevs[i], prev_bytes[i]))
+                return bad(i == 3 ? "moments must not alias prev_moments (ping-pong two planes)" : "moments overlaps a prev_* plane");
+        for (int o = 0; o < 3; o++)
+            if (overlaps(outs[o], out_bytes[o], prev_moments, n * 8u)) return bad("an output overlaps prev_moments");
+        if (dynamic && overlaps(moments, n * 8u, prim_motion, table_bytes)) return bad("moments overlaps the prim_motion table");
+    }
+    if (n == 0) return RT_OK;
+    return launch_temporal_moments(P, dynamic, prim_motion, num_prims, reset ? nullptr : prev_moments, moments, stream);
+}
+
 int rt_scene_motion(const rt_hittable_desc* prev, const rt_hittable_desc* cur, uint32_t num_hittables, float* table) {
     if (num_hittables && (!prev || !cur || !table)) {
         set_error("rt_scene_motion: NULL argument with num_hittables > 0");

@@ -153,6 +153,10 @@ struct TemporalParams {
 int launch_temporal(const TemporalParams& P, void* stream);
 // rt_temporal_dynamic's launch: prim_motion = num_prims float4 entries on the device (may be NULL with RT_TEMPORAL_RESET)
 int launch_temporal_dynamic(const TemporalParams& P, const float* prim_motion, uint32_t num_prims, void* stream);
+// rt_temporal_moments' launch: the static body (dynamic = false: the table is not passed on) or the dynamic one, plus the
+// float2 moments planes on the device (prev_moments may be NULL with RT_TEMPORAL_RESET)
+int launch_temporal_moments(const TemporalParams& P, bool dynamic, const float* prim_motion, uint32_t num_prims,
+                            const float* prev_moments, float* moments, void* stream);
 
 inline float bits_to_float(uint32_t u) {
     float f;

@@ -20,6 +20,9 @@
 // rt_temporal_dynamic is a second kernel over the same body: between the world point and the camera
 // inverse it moves the point by its hittable's entry of a per-hittable motion table (rt_scene_motion), so history
 // survives object edits; tests/test_dynamic_host.py temporal_dynamic_reference restates it.
+// rt_temporal_moments adds two more kernels over the same body: beside the colour they accumulate the
+// first and second moment of the pixel's luminance (one 8-byte load per counting tap, issued with the history loads, and
+// one 8-byte store), from which rt_denoise_variance takes each pixel's own noise level.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -54,8 +57,12 @@ __device__ __forceinline__ v3 ray_start(const TemporalCamera& C, const float u, 
 // hittable's motion entry table[id] = (o.xyz, s), moves the world point to where that surface point was in the previous
 // scene before the camera inverse.  The static build holds none of it (if constexpr): temporal_kernel keeps the 63
 // VGPRs and 905 instructions it had before the second kernel existed.
-template <bool DYNAMIC>
-__device__ __forceinline__ void temporal_body(const TemporalParams& P, const float4* table, const uint32_t num_prims) {
+// MOMENTS = true is rt_temporal_moments: the counting taps also fetch prev_moments = (m1, m2) and the
+// pixel's luminance l and l·l are blended into their weighted mean with the colour's alpha.  Again if constexpr: the
+// two kernels without moments hold none of it.
+template <bool DYNAMIC, bool MOMENTS>
+__device__ __forceinline__ void temporal_body(const TemporalParams& P, const float4* table, const uint32_t num_prims,
+                                              const float2* prev_moments, float2* moments) {
     const uint32_t x = blockIdx.x * kTpTileW + threadIdx.x, y = blockIdx.y * kTpTileH + threadIdx.y;
     if (x >= P.width || y >= P.height) return;
     const int W = (int)P.width, H = (int)P.height;
@@ -68,6 +75,11 @@ __device__ __forceinline__ void temporal_body(const TemporalParams& P, const flo
     }
     float4 out = make_float4(c.x, c.y, c.z, 1.0f);
     float2 mv = make_float2(0.0f, 0.0f);
+    float2 lm = make_float2(0.0f, 0.0f), mo = lm;  // (l, l·l) of this frame's colour; the moments written
+    if constexpr (MOMENTS) {
+        const float l = (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z;
+        lm = mo = make_float2(l, l * l);
+    }
     const int id = P.prim_id[pix];
     // 1a. the hittable's motion entry: one 16-byte load per lane (neighbouring lanes mostly share the entry: the table
     // is a few cache lines); an id beyond the table or s == 0 means no history
@@ -132,16 +144,19 @@ __device__ __forceinline__ void temporal_body(const TemporalParams& P, const flo
                     if (ok[k]) pid[k] = P.prev_prim_id[at[k]];
                 }
                 float4 hq[4], nq[4];
+                float2 mq[4];
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     hq[k] = nq[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    mq[k] = make_float2(0.0f, 0.0f);
                     ok[k] = ok[k] && pid[k] == id;
                     if (ok[k]) {
                         hq[k] = ((const float4*)P.prev_history)[at[k]];
                         nq[k] = ((const float4*)P.prev_normal_depth)[at[k]];
+                        if constexpr (MOMENTS) mq[k] = prev_moments[at[k]];
                     }
                 }
-                float S = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f;
+                float S = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sl = 0.0f, sm1 = 0.0f, sm2 = 0.0f;
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
                     const float ndot = (nd.x * nq[k].x + nd.y * nq[k].y) + nd.z * nq[k].z;
@@ -152,6 +167,10 @@ __device__ __forceinline__ void temporal_body(const TemporalParams& P, const flo
                     sg = sg + wk * hq[k].y;
                     sb = sb + wk * hq[k].z;
                     sl = sl + wk * hq[k].w;
+                    if constexpr (MOMENTS) {
+                        sm1 = sm1 + wk * mq[k].x;
+                        sm2 = sm2 + wk * mq[k].y;
+                    }
                 }
                 if (S >= kMinWeight) {
                     // 5. blend
@@ -159,25 +178,44 @@ __device__ __forceinline__ void temporal_body(const TemporalParams& P, const flo
                     const float N = fminf(sl / S + 1.0f, P.max_history);
                     const float alpha = 1.0f / N;
                     out = make_float4(hr + alpha * (c.x - hr), hg + alpha * (c.y - hg), hb + alpha * (c.z - hb), N);
+                    if constexpr (MOMENTS) {
+                        const float m1 = sm1 / S, m2 = sm2 / S;
+                        mo = make_float2(m1 + alpha * (lm.x - m1), m2 + alpha * (lm.y - m2));
+                    }
                 }
             }
         }
     }
     ((float4*)P.history)[pix] = out;
+    if constexpr (MOMENTS) moments[pix] = mo;
     if (P.motion) ((float2*)P.motion)[pix] = mv;
     // the render kernels' epilogue (Kernel.cu:152-157)
     if (P.pos) P.pos[pix] = rgb_to_int(255.0f * sqrtf(out.x), 255.0f * sqrtf(out.y), 255.0f * sqrtf(out.z));
 }
 
 __global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_kernel(const TemporalParams P) {
-    temporal_body<false>(P, nullptr, 0u);
+    temporal_body<false, false>(P, nullptr, 0u, nullptr, nullptr);
 }
 
 // rt_temporal_dynamic: the same launch shape; `table` holds num_prims float4 entries (never read with RT_TEMPORAL_RESET)
 __global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_dynamic_kernel(const TemporalParams P,
                                                                                const float4* __restrict__ table,
                                                                                const uint32_t num_prims) {
-    temporal_body<true>(P, table, num_prims);
+    temporal_body<true, false>(P, table, num_prims, nullptr, nullptr);
+}
+
+// rt_temporal_moments without and with a motion table: the bodies above plus the moments (prev_moments is never read with
+// RT_TEMPORAL_RESET)
+__global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_moments_kernel(const TemporalParams P,
+                                                                               const float2* __restrict__ prev_moments,
+                                                                               float2* __restrict__ moments) {
+    temporal_body<false, true>(P, nullptr, 0u, prev_moments, moments);
+}
+
+__global__ __launch_bounds__(kTpTileW * kTpTileH) void temporal_dynamic_moments_kernel(
+    const TemporalParams P, const float4* __restrict__ table, const uint32_t num_prims,
+    const float2* __restrict__ prev_moments, float2* __restrict__ moments) {
+    temporal_body<true, true>(P, table, num_prims, prev_moments, moments);
 }
 
 }  // namespace dev
@@ -204,6 +242,25 @@ int launch_temporal_dynamic(const TemporalParams& P, const float* prim_motion, u
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_error(std::string("rt_temporal_dynamic: kernel launch: ") + hipGetErrorString(e));
+        return RT_ERR_LAUNCH;
+    }
+    return RT_OK;
+}
+
+int launch_temporal_moments(const TemporalParams& P, const bool dynamic, const float* prim_motion, uint32_t num_prims,
+                            const float* prev_moments, float* moments, void* stream) {
+    const dim3 block(dev::kTpTileW, dev::kTpTileH);
+    const dim3 grid((P.width + dev::kTpTileW - 1) / dev::kTpTileW, (P.height + dev::kTpTileH - 1) / dev::kTpTileH);
+    (void)hipGetLastError();
+    if (dynamic)
+        hipLaunchKernelGGL(dev::temporal_dynamic_moments_kernel, grid, block, 0, (hipStream_t)stream, P,
+                           (const float4*)prim_motion, num_prims, (const float2*)prev_moments, (float2*)moments);
+    else
+        hipLaunchKernelGGL(dev::temporal_moments_kernel, grid, block, 0, (hipStream_t)stream, P,
+                           (const float2*)prev_moments, (float2*)moments);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_error(std::string("rt_temporal_moments: kernel launch: ") + hipGetErrorString(e));
         return RT_ERR_LAUNCH;
     }
     return RT_OK;

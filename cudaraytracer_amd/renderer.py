@@ -126,6 +126,11 @@ class Renderer:
         self.motion = None           # temporal(motion=True): (local_rows × W × 2) float32
         self._temporal_pos = None
         self._prim_motion = None     # temporal(prim_motion=...): the device table of the last call
+        self.moments = None          # temporal(moments=True): (local_rows × W × 2) float32, luminance moments (m1, m2)
+        self._moments_spare = None   # ... the plane the next call writes
+        self.denoised_variance = None          # denoise_variance(): (local_rows × W × 4) float32, rgb + variance
+        self._denoise_variance_scratch = None  # ... its planes, allocated once
+        self._denoise_variance_pos = None
 
     def tiling(self) -> abi.Tiling:
         return abi.Tiling(self.band_rows, self.num_ranks, self.rank, self.local_rows)
@@ -255,7 +260,8 @@ class Renderer:
         return self._denoise_pos
 
     def temporal(self, max_history: int = 32, depth_tol: float = 0.05, normal_tol: float = 0.2,
-                 source: str = "radiance", reset: bool = False, motion: bool = False, prim_motion=None) -> torch.Tensor:
+                 source: str = "radiance", reset: bool = False, motion: bool = False, prim_motion=None,
+                 moments: bool = False) -> torch.Tensor:
         """Reprojected temporal accumulation (rt_temporal) of the last frame's `radiance` or `accum` plane into
         `self.history` (rows, W, 4: rgb, history length), asynchronous on torch's current stream; whole frames only.
         Call once per frame after render() and gbuffer(..., keep_previous=True): the last call's history is looked up
@@ -264,7 +270,10 @@ class Renderer:
         accumulated colour; denoise(source="history") filters it.
         prim_motion: the (n, 4) float32 per-hittable motion table of an object edit between the two frames
         (scenes.scene_motion; a torch tensor on this device or a numpy array, which is uploaded): the pass then runs as
-        rt_temporal_dynamic and history follows the moved hittables.  None keeps the rt_temporal call."""
+        rt_temporal_dynamic and history follows the moved hittables.  None keeps the rt_temporal call.
+        moments=True runs the pass as rt_temporal_moments (with or without the table): `self.moments` (rows, W, 2), the
+        accumulated first and second moment of the luminance, ping-pongs beside the history; denoise_variance() reads
+        it.  A call that finds no moments plane of the call before behaves as reset=True."""
         if source not in ("radiance", "accum"):
             raise ValueError(f"source must be 'radiance' or 'accum', not {source!r}")
         color = self.radiance if source == "radiance" else self.accum
@@ -281,6 +290,7 @@ class Renderer:
         if motion and self.motion is None:
             self.motion = torch.zeros(shape + (2,), dtype=torch.float32, device=self.device)
         reset = reset or self.history is None or self.prev_normal_depth is None or self.prev_inputs is None
+        reset = reset or (moments and self.moments is None)
         a = abi.TemporalArgs()
         a.color = color.data_ptr()
         a.normal_depth, a.prim_id = self.normal_depth.data_ptr(), self.prim_id.data_ptr()
@@ -296,9 +306,8 @@ class Renderer:
         a.depth_tol, a.normal_tol = depth_tol, normal_tol
         a.tiling = self.tiling()
         a.inputs = self._gbuffer_inputs
-        if prim_motion is None:
-            check(lib().rt_temporal(C.byref(a), C.c_void_p(self.stream())), "rt_temporal")
-        else:
+        table = None
+        if prim_motion is not None:
             table = prim_motion
             if not isinstance(table, torch.Tensor):
                 table = torch.from_numpy(np.array(table, dtype=np.float32))
@@ -307,10 +316,62 @@ class Renderer:
             if table.numel() % 4:
                 raise ValueError("temporal: prim_motion holds four floats per hittable")
             self._prim_motion = table  # (kept until the next call: the launch is asynchronous)
-            check(lib().rt_temporal_dynamic(C.byref(a), C.c_void_p(table.data_ptr() if table.numel() else None),
-                                            table.numel() // 4, C.c_void_p(self.stream())), "rt_temporal_dynamic")
+        table_ptr = C.c_void_p(table.data_ptr() if table is not None and table.numel() else None)
+        if moments:
+            out_m = self._moments_spare
+            if out_m is None:
+                out_m = torch.zeros(shape + (2,), dtype=torch.float32, device=self.device)
+            if table is not None and not table.numel():
+                raise ValueError("temporal: moments=True takes prim_motion=None or a table with entries")
+            check(lib().rt_temporal_moments(C.byref(a), table_ptr, table.numel() // 4 if table is not None else 0,
+                                            C.c_void_p(None if reset else self.moments.data_ptr()),
+                                            C.c_void_p(out_m.data_ptr()), C.c_void_p(self.stream())), "rt_temporal_moments")
+            self.moments, self._moments_spare = out_m, self.moments
+        else:
+            if table is None:
+                check(lib().rt_temporal(C.byref(a), C.c_void_p(self.stream())), "rt_temporal")
+            else:
+                check(lib().rt_temporal_dynamic(C.byref(a), table_ptr, table.numel() // 4, C.c_void_p(self.stream())),
+                      "rt_temporal_dynamic")
+            if self.moments is not None:  # a frame without moments: the plane no longer belongs to the history
+                self._moments_spare, self.moments = self.moments, None
         self.history, self._history_spare = out, self.history
         return self._temporal_pos
+
+    def denoise_variance(self, iterations: int = 3, sigma_l: float = 1.0, sigma_n: float = 0.1, sigma_z: float = 0.05,
+                         min_history: int = 4) -> np.ndarray:
+        """Variance-guided à-trous filter (rt_denoise_variance) of temporal(moments=True)'s `history` and `moments`,
+        guided by the last gbuffer(); whole frames only.  Returns the RGBA8 image like image() and keeps the float result
+        (rgb, filtered variance) in `self.denoised_variance`."""
+        pos = self.denoise_variance_async(iterations, sigma_l, sigma_n, sigma_z, min_history)
+        return pos.cpu().numpy().view(np.uint32).reshape(self.local_rows, self.width)
+
+    def denoise_variance_async(self, iterations: int = 3, sigma_l: float = 1.0, sigma_n: float = 0.1,
+                               sigma_z: float = 0.05, min_history: int = 4) -> torch.Tensor:
+        """denoise_variance() without the copy to the host: asynchronous on torch's current stream; returns the device
+        RGBA8 framebuffer."""
+        if self.history is None or self.moments is None:
+            raise RTError("denoise_variance: no history and moments planes (call temporal(moments=True) first)")
+        if self.normal_depth is None:
+            raise RTError("denoise_variance: no G-buffer (call gbuffer() first)")
+        L = lib()
+        n = self.width * self.local_rows
+        if self.denoised_variance is None:
+            self.denoised_variance = torch.zeros((self.local_rows, self.width, 4), dtype=torch.float32, device=self.device)
+            self._denoise_variance_pos = torch.zeros(n, dtype=torch.int32, device=self.device)
+        need = int(L.rt_denoise_variance_scratch_bytes(self.width, self.height, 6))  # once, for any iteration count
+        if self._denoise_variance_scratch is None and need:
+            self._denoise_variance_scratch = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        a = abi.DenoiseVarianceArgs()
+        a.color, a.moments = self.history.data_ptr(), self.moments.data_ptr()
+        a.normal_depth, a.prim_id = self.normal_depth.data_ptr(), self.prim_id.data_ptr()
+        a.out_color, a.pos = self.denoised_variance.data_ptr(), self._denoise_variance_pos.data_ptr()
+        a.scratch = self._denoise_variance_scratch.data_ptr() if self._denoise_variance_scratch is not None else None
+        a.width, a.height, a.iterations, a.min_history = self.width, self.height, iterations, min_history
+        a.sigma_l, a.sigma_n, a.sigma_z = sigma_l, sigma_n, sigma_z
+        a.tiling = self.tiling()
+        check(L.rt_denoise_variance(C.byref(a), C.c_void_p(self.stream())), "rt_denoise_variance")
+        return self._denoise_variance_pos
 
     def image(self) -> np.ndarray:
         """Local framebuffer as (local_rows, W) uint32 RGBA8 (row 0 = bottom of the image)."""

@@ -183,8 +183,9 @@ const char* rt_version(void);
 /* Version of this C ABI (structure layouts, counter words, entry points); a caller built against an older header
  * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
  * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal.  9: rt_scene_motion, rt_temporal_dynamic,
- * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE.  12: RT_TUNE_PATH_END_STEP. */
-#define RT_ABI_VERSION 12
+ * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE.  12: RT_TUNE_PATH_END_STEP.
+ * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes. */
+#define RT_ABI_VERSION 13
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -548,6 +549,64 @@ int rt_temporal(const rt_temporal_args* args, rt_stream stream);
  * surfaces lag by up to max_history frames (those surfaces keep their history: nothing they are tested by changed); a
  * hittable whose material changed needs its entry zeroed by the caller. */
 int rt_temporal_dynamic(const rt_temporal_args* args, const float* prim_motion, uint32_t num_prims, rt_stream stream);
+
+/* rt_temporal (prim_motion == NULL, which requires num_prims == 0) or rt_temporal_dynamic (otherwise) that also
+ * accumulates the first and second moment of each pixel's luminance: what rt_denoise_variance below takes a pixel's own
+ * noise level from (Schied et al. 2017).  prev_moments and moments are float2 planes, (m1, m2) per pixel, height × width.
+ * The definition is the respective pass's steps 0-5 with three additions:
+ *  - Luminance.  With c the pixel's colour of step 0, l = (0.2126f·c.r + 0.7152f·c.g) + 0.0722f·c.b, in binary32 with no
+ *    contraction.
+ *  - Step 4.  The counting taps also fetch prev_moments; with the same weights, M = Σ w·m / S.
+ *  - Step 5.  moments(p) = M + alpha·((l, l·l) − M) with the same alpha; where there is no history, the pixel is a miss
+ *    or RT_TEMPORAL_RESET is set, moments(p) = (l, l·l).
+ * history, motion and pos are bit for bit what rt_temporal / rt_temporal_dynamic writes for the same arguments.
+ * Arguments: rt_temporal_dynamic's checks apply (a non-NULL table's alignment and overlap).  moments must be non-NULL,
+ * prev_moments too unless RT_TEMPORAL_RESET is set; moments must not overlap any input, prev_* plane (prev_moments
+ * included), other output or the table, and no output may overlap prev_moments (RT_ERR_INVALID_ARGUMENT, with a message
+ * naming moments): the caller ping-pongs two moments planes beside the two history planes.  One launch, one 8-byte load
+ * per counting tap and one 8-byte store more than the pass without moments; no atomics: two calls give the same bits. */
+int rt_temporal_moments(const rt_temporal_args* args, const float* prim_motion, uint32_t num_prims,
+                        const float* prev_moments, float* moments, rt_stream stream);
+
+/* Variance-guided à-trous filter (the spatial half of SVGF, Schied et al. 2017) of a whole frame: rt_denoise's filter
+ * with its fixed colour tolerance replaced by sigma_l standard deviations of each pixel's own luminance noise, taken
+ * from rt_temporal_moments' plane; the variance is filtered along with the colour.  e_n, e_z, h and the validity rule
+ * (prim_id >= 0) are exactly rt_denoise's; lum() is rt_temporal_moments' luminance.  No demodulation.
+ *  - Variance stage.  For a valid pixel p with N = max(color.w, 1): if N >= min_history, v = max(0, m2 − m1·m1); else
+ *    over q = p + (dx, dy), dx, dy in -3..3, inside the frame and valid, with g = expf(−(e_n + e_z)):
+ *    m~ = Σ g·m(q) / Σ g and v = 4·max(0, m~2 − m~1·m~1) (the centre always counts; the factor 4 is the SVGF sample
+ *    code's for short histories: the centre's own sample dominates m~, so the window's estimate is low).
+ *    var_0(p) = v / N, c_0 = color.rgb.
+ *  - Iteration i = 0 .. iterations-1, step s = 2^i.  v~(p) = Σ k·var_i(q) / Σ k over the 3×3 neighbours at distance 1,
+ *    inside the frame and valid, k = (1/4, 1/2, 1/4) ⊗ (1/4, 1/2, 1/4).  Over q = p + s·(dx, dy), dx, dy in -2..2,
+ *    inside the frame and valid:
+ *      w = h[dx+2]·h[dy+2]·expf(−(e_n + e_z + |lum(c_i(p)) − lum(c_i(q))| / (sigma_l·sqrtf(v~(p) + 1e-6f)))),
+ *      c_{i+1}(p) = Σ w·c_i(q) / Σ w,   var_{i+1}(p) = Σ w²·var_i(q) / (Σ w)².
+ * A miss (prim_id < 0) passes through with variance 0.  Defaults worth starting from: iterations 3, sigma_l 1.0,
+ * sigma_n 0.1, sigma_z 0.05, min_history 4.
+ * One launch for the variance stage and one per iteration, no atomics: two calls on the same inputs give the same bits.
+ * Intermediate planes (rgb, variance) live in `scratch` (device memory of rt_denoise_variance_scratch_bytes bytes; NULL
+ * only when that is 0).  out_color, pos and scratch must not overlap any input or each other; whole frames only. */
+typedef struct rt_denoise_variance_args {
+    const float* color;        /* float4: rgb, w = history length (rt_temporal's history plane); N = max(w, 1) */
+    const float* moments;      /* float2, rt_temporal_moments' plane of the same frame */
+    const float* normal_depth; /* rt_gbuffer_args.normal_depth */
+    const int32_t* prim_id;    /* rt_gbuffer_args.prim_id */
+    float* out_color;          /* optional float4: rgb, w = the filtered variance (0 on a miss) */
+    uint32_t* pos;             /* optional RGBA8 through the render kernels' epilogue; at least one output */
+    void* scratch;             /* rt_denoise_variance_scratch_bytes */
+    uint32_t width, height;
+    uint32_t iterations;       /* 1..6 */
+    uint32_t flags;            /* must be 0 */
+    float sigma_l, sigma_n, sigma_z;   /* all > 0; start from 1.0, 0.1, 0.05 */
+    uint32_t min_history;              /* 1..4096; start from 4 */
+    uint32_t reserved[2];              /* must be 0 */
+    rt_tiling tiling;                  /* whole frame only */
+} rt_denoise_variance_args;            /* 112 B */
+/* Bytes of rt_denoise_variance_args.scratch for a frame (0 for an empty frame). */
+uint64_t rt_denoise_variance_scratch_bytes(uint32_t width, uint32_t height, uint32_t iterations);
+/* The filter on `stream`, asynchronous; status codes and rt_last_error as rt_render. */
+int rt_denoise_variance(const rt_denoise_variance_args* args, rt_stream stream);
 
 /* Tuning/benchmark knob (per thread): the kernel rt_render launches.  -1 = automatic: 3 from 64 spp; below,
  * the faster of 3 and 4 as timed on the first frames of each (device, stream, scene, frame shape, spp, depth,

@@ -19,6 +19,13 @@ motion and 4 of RGBA8 written: 100.  `history_share` is the share of pixels that
 table of rt_scene_motion (uploaded outside the timed region) holds a non-identity entry.  rt_temporal on those frames
 ignores the sphere's motion; its time is the yardstick (`ratio_to_temporal`).  The bytes are rt_temporal's: the table's
 80 bytes stay in cache.  --dynamic-json writes the two entries to a file (profiles/temporal_dynamic_bench.json).
+
+`temporal_moments` times rt_temporal_moments (without the table) in the same loop on the same planes, its moments planes
+ping-ponging once per frame: rt_temporal's 100 bytes per pixel plus 8 of previous moments gathered and 8 written, 116.
+`denoise_variance_n1/3/5` time rt_denoise_variance on that call's history and moments (defaults otherwise): the variance
+stage reads 44 bytes per pixel and writes 16, each iteration reads the colour/variance and normal/depth planes and writes
+one, the last also the RGBA8 framebuffer.  Both carry their ratios to rt_temporal and to rt_denoise (same N, and N = 3)
+of the same run.  --variance-json writes these entries to a file (profiles/variance_bench.json).
 """
 import argparse, json, os, statistics, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -33,6 +40,7 @@ ap.add_argument("--width", type=int, default=0, help="override the config's size
 ap.add_argument("--height", type=int, default=0)
 ap.add_argument("--texture-size", default="", help="WxH of the three textures (default: the config's 8192x4096)")
 ap.add_argument("--dynamic-json", default="", help="also write the temporal / temporal_dynamic entries to this file")
+ap.add_argument("--variance-json", default="", help="also write the temporal_moments / denoise_variance entries to this file")
 args = ap.parse_args()
 
 cfg = scenes.CONFIGS["c5"]
@@ -71,7 +79,8 @@ def timed(fn) -> float:
     return e0.elapsed_time(e1)
 
 
-times = {"render": [], "gbuffer": [], "temporal": [], "temporal_dynamic": [], **{f"denoise_n{n}": [] for n in ITER}}
+times = {"render": [], "gbuffer": [], "temporal": [], "temporal_dynamic": [], "temporal_moments": [],
+         **{f"denoise_n{n}": [] for n in ITER}, **{f"denoise_variance_n{n}": [] for n in ITER}}
 total = args.warmup + args.frames
 hittables = dragged(0)
 history_share = {}
@@ -87,18 +96,24 @@ for f in range(total):
     torch.cuda.synchronize()
     t = {"render": timed(lambda: r.render(ds, cfg.spp, cfg.depth, inp, flags=abi.RT_FLAG_ACCUMULATE, count=False)),
          "gbuffer": timed(lambda: r.gbuffer(ds, inp, keep_previous=True))}
-    # both passes on the same planes; which of the two runs first (and finds the caches cold) alternates by frame
+    # the three passes on the same planes; which of them runs first (and finds the caches cold) rotates by frame
     calls = {"temporal": lambda: r.temporal(source="accum", motion=True),
-             "temporal_dynamic": lambda: r.temporal(source="accum", motion=True, prim_motion=table)}
-    order = ("temporal", "temporal_dynamic") if f % 2 == 0 else ("temporal_dynamic", "temporal")
+             "temporal_dynamic": lambda: r.temporal(source="accum", motion=True, prim_motion=table),
+             "temporal_moments": lambda: r.temporal(source="accum", motion=True, moments=True)}
+    names = ("temporal", "temporal_dynamic", "temporal_moments")
+    order = names[f % 3:] + names[:f % 3]
     for i, name in enumerate(order):
-        if i and r._history_spare is not None:  # (not the first frame) hand the planes back: the second call reads and
+        if i and r._history_spare is not None:  # (not the first frame) hand the planes back: a later call reads and
             r.history, r._history_spare = r._history_spare, r.history  # writes what the first did
+        kept = (r.moments, r._moments_spare)
         t[name] = timed(calls[name])
+        if name != "temporal_moments":  # (a call without moments drops the renderer's plane: the next frame needs it)
+            r.moments, r._moments_spare = kept
         if f == total - 1:
             history_share[name] = float((r.history[..., 3] > 1.0).float().mean().item())
     for n in ITER:
         t[f"denoise_n{n}"] = timed(lambda: r.denoise_async(iterations=n, source="accum"))
+        t[f"denoise_variance_n{n}"] = timed(lambda: r.denoise_variance_async(iterations=n))
     if f >= args.warmup:
         for k, v in t.items():
             times[k].append(v)
@@ -127,4 +142,24 @@ for n in ITER:
     m, b = ms[f"denoise_n{n}"], denoise_bytes(n)
     out[f"denoise_n{n}"] = {"ms": round(m, 4), "bytes": b, "GB_per_s": round(b / m / 1e6, 1),
                             "ms_per_iteration": round(m / n, 4), "ratio_to_render": round(m / ms["render"], 3)}
+mb = npix * 116
+out["temporal_moments"] = {"ms": round(ms["temporal_moments"], 4), "bytes": mb,
+                           "GB_per_s": round(mb / ms["temporal_moments"] / 1e6, 1),
+                           "ratio_to_render": round(ms["temporal_moments"] / ms["render"], 3),
+                           "ratio_to_temporal": round(ms["temporal_moments"] / ms["temporal"], 3),
+                           "ratio_to_denoise_n3": round(ms["temporal_moments"] / ms["denoise_n3"], 3),
+                           "history_share": round(history_share["temporal_moments"], 3)}
+for n in ITER:
+    m, b = ms[f"denoise_variance_n{n}"], npix * (60 + 48 * n + 4)
+    out[f"denoise_variance_n{n}"] = {"ms": round(m, 4), "bytes": b, "GB_per_s": round(b / m / 1e6, 1),
+                                     "ratio_to_render": round(m / ms["render"], 3),
+                                     "ratio_to_temporal": round(m / ms["temporal"], 3),
+                                     "ratio_to_denoise_same_n": round(m / ms[f"denoise_n{n}"], 3),
+                                     "ratio_to_denoise_n3": round(m / ms["denoise_n3"], 3)}
+if args.variance_json:
+    with open(args.variance_json, "w") as fh:
+        keys = ("config", "workload", "frames", "warmup", "device", "render_ms", "temporal", "denoise_n1", "denoise_n3",
+                "denoise_n5", "temporal_moments", "denoise_variance_n1", "denoise_variance_n3", "denoise_variance_n5")
+        json.dump({k: out[k] for k in keys}, fh)
+        fh.write("\n")
 print(json.dumps(out), flush=True)

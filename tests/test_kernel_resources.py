@@ -44,10 +44,12 @@ def kernel_metadata(tmp_path):
     lib = tmp_path / "librt_hip.so"
     shutil.copy(LIB, lib)
     subprocess.run([f"{LLVM}/llvm-objdump", "--offloading", str(lib)], check=True, capture_output=True, cwd=tmp_path)
-    co = [f for f in os.listdir(tmp_path) if f.endswith("gfx950")]
+    # one code object per .hip file: all of them (the directory's listing order differs between file systems, and the
+    # first entry is render.hip's on some only)
+    co = sorted(f for f in os.listdir(tmp_path) if f.endswith("gfx950"))
     assert co, os.listdir(tmp_path)
-    notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(tmp_path / co[0])], check=True,
-                           capture_output=True, text=True).stdout
+    notes = "\n".join(subprocess.run([f"{LLVM}/llvm-readelf", "--notes", str(tmp_path / c)], check=True,
+                                     capture_output=True, text=True).stdout for c in co)
     meta, name = {}, None
     for line in notes.splitlines():
         m = re.match(r"\s+\.(name|private_segment_fixed_size|vgpr_count|vgpr_spill_count|sgpr_spill_count):\s+(\S+)", line)

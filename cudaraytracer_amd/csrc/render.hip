@@ -3950,6 +3950,124 @@ thread_local float g_last_host_ms = -1.0f;  // LaunchKernel: host time of the sc
 thread_local int g_variant = -1;
 thread_local int g_last_variant = -1;  // the variant the last rt_render on this thread launched
 
+// ----- rt_set_tuning's knobs (per thread; kKnobs below holds their ranges) ---------------------------
+// RT_TUNE_REGEN_THRESHOLD: 56 together with the live-pixel cap below (the pair's plateau, 56-64 x 52-60/64, is
+// flat within 0.3 %; 40 without the cap was round 2's optimum: profiles/r03o_sweep_regen_live_frac.txt)
+thread_local int g_regen_threshold = 56;
+// RT_TUNE_REGEN_LIVE_FRAC: v3's regeneration threshold is capped at 48/64 of the wave's live pixels, so a wave whose
+// pixels are finishing keeps tracing until most of its remaining lanes are done instead of shading a few lanes per
+// leaf pass; with it a higher base threshold pays (C2 −2.1 % for the pair against 40 without the cap, C4 −2.4 %,
+// C3 ±0.2 %: profiles/r03o_sweep_regen_live_frac.txt; 48 rather than 56 once the leaf-break rule is on, −0.6 %:
+// profiles/r03s_ab_node_min_cap.txt)
+thread_local int g_regen_live_frac = 48;
+// RT_TUNE_LEAF_BREAK: leave the node loop for the leaf tests once at most 3 traversing lanes still lack a leaf
+// (with the threshold pair above: C2 −2.4 %, C4 −3.5 %, C3 ±0; round 2 measured −1.2 / +1 % at 2 with threshold 40
+// and no cap: profiles/r03r_ab_leaf_break.txt)
+thread_local int g_leaf_break = 3;
+thread_local int g_lds_pad = 0;         // RT_TUNE_LDS_PAD, diagnostic: extra LDS bytes per wave (occupancy experiments)
+thread_local int g_adaptive_order = 1;  // RT_TUNE_ADAPTIVE_ORDER
+// RT_TUNE_FLAT_MAX: scenes of at most this many primitives run the flat kernels (variants 5, 6) where the automatic
+// choice would run v3 / v4.  RT_TUNE_RIUS_TRIPS: the tile flat kernel's RandomInUnitSphere attempts per pass before a
+// rejecting lane defers the rest of the call to the next pass (0 = unbounded; 4: C3's optimum, a wave otherwise runs
+// the loop as long as its unluckiest lane).  RT_TUNE_RIUS_TRIPS_PERSISTENT: the same for the persistent flat kernel,
+// unbounded by default — a C5 frame is bound by its last pixels' chains of passes, and a deferred call adds a pass to
+// one (C5 0.262 -> 0.253 ms per step unbounded, K = 4 / 6 / 8: 0.262 / 0.260 / 0.255; profiles/r05u_c5_rius_trips.txt)
+thread_local int g_flat_max = 16;
+thread_local int g_rius_trips = 4;
+thread_local int g_rius_trips_persistent = 0;
+// RT_TUNE_PREFETCH_STOP: the persistent flat kernel's lanes take their next pixel ahead (kFlatPrefetch) only while their
+// wave's queue head holds more than 1/value of its range (0 = never); kPrefetchStop (8) by default
+thread_local int g_prefetch_stop = (int)dev::kPrefetchStop;
+thread_local int g_persistent_waves = 0;  // RT_TUNE_PERSISTENT_WAVES; 0: occupancy query
+constexpr uint32_t kQueueMaxStride = 4096;  // bytes between heads (RT_TUNE_QUEUE_STRIDE)
+thread_local int g_queue_stride = 128;  // RT_TUNE_QUEUE_STRIDE: bytes between the v4 kernel's queue heads
+// RT_TUNE_QUEUE_CHUNK: work indices per queue atomic while the head has plenty left.  128 since the texel gather
+// overlaps RandomInUnitSphere: C5 -3.6 % against 64 (0.2525 vs 0.2620 ms, 6 alternations; 192 / 256 lose,
+// profiles/r05ag_c5_queue_chunk.txt); round 3 had measured 64..256 within 3 %
+thread_local int g_queue_chunk = 128;
+thread_local int g_queue_prefetch = 32; // RT_TUNE_QUEUE_PREFETCH: fetch the next chunk ahead at this many indices left
+thread_local int g_queue_guide = 0;     // RT_TUNE_QUEUE_GUIDE: guided chunks, head_left / (waves per head × this)
+thread_local int g_queue_min = 16;      // RT_TUNE_QUEUE_MIN_CHUNK: the guided chunks' floor
+// RT_TUNE_QUEUE_RESET: 1 = rt_render zeroes the persistent kernels' queue slot per launch (and they skip queue_release)
+thread_local int g_queue_host_reset = 0;
+// RT_TUNE_PERSISTENT_GROUP: the persistent flat kernel's 16-wave workgroups drawing chunks from the queue heads (2,
+// default: GroupQueue), with static tile shares (1: GroupShare), or the round-5 one-wave workgroups on the per-wave
+// queue alone (0); profiles/r06b_ab_c5_group_shares.txt
+thread_local int g_persistent_group = 2;
+// RT_TUNE_GROUP_TAIL: permille of the frame's tiles left to the per-wave queue behind the groups' static shares
+thread_local int g_group_tail = 0;
+// RT_TUNE_GROUP_ORDER: the shares' tiles interleaved (0: tile g + k·groups) or in golden-ratio order (1)
+thread_local int g_group_order = 0;
+// RT_TUNE_GROUP_CHUNK: positions per chunk of the workgroup chunk queue (RT_TUNE_PERSISTENT_GROUP 2)
+thread_local int g_group_chunk = 1024;
+// RT_TUNE_GROUP_WAVES: waves per workgroup of the GROUP builds (4, 8, 12 or 16)
+thread_local int g_group_waves = 16;
+// RT_TUNE_GROUP_LINGER_US: a finished workgroup waits up to this long for the grid's others before it exits (0: off)
+thread_local int g_group_linger_us = 0;
+// RT_TUNE_TILE_ENTRIES: 1 (default) = the v3 kernels start a full tile's camera rays at the tile's candidate leaves
+// (rt_tile_entry.h; 16-bit-reference scenes, band_rows a multiple of 8), 0 = every ray starts at the root (A/B, tests)
+thread_local int g_tile_entries = 1;
+// RT_TUNE_CAMERA_RESOLVE: 1 (default) = with the entry records, a v3 shading pass ends its cleared misses ahead of
+// shade() and resolves their next camera rays by a scan of the tile's record (v3_resolve_camera), for records of at
+// most kCameraResolveCap primitives; 2..32 = the same with that cap (A/B, tests); 0 = off: every camera ray takes the
+// leaf chain (the parent's behaviour)
+thread_local int g_camera_resolve = 1;
+constexpr uint32_t kCameraResolveCap = 8;
+constexpr int kCameraResolveMax = 32;  // a record's eight references hold at most four primitives each
+// RT_TUNE_PATH_END_STEP: 1 (default) = where the pre-step scans a wave's record, every path end of the wave (absorption,
+// the depth limit, an emitter, a camera ray that missed) and the pixel's first camera ray go through the pre-step too:
+// no lane holds a camera ray's leaf chain through a traversal call; 0 = only cleared misses do (A/B, tests)
+thread_local int g_path_end_step = 1;
+
+// One row per rt_tuning_key, in the enum's order: where the value lives, the values rt_set_tuning accepts (lo..hi,
+// multiples of `step`, powers of two where `pow2`) and what it says when it refuses one.
+struct Knob {
+    int& (*at)();
+    int lo, hi, step;
+    bool pow2;
+    const char* refusal;
+};
+const Knob kKnobs[] = {
+    {[]() -> int& { return g_regen_threshold; }, 1, 64, 1, false, "rt_set_tuning: regen threshold must be in [1, 64]"},
+    {[]() -> int& { return g_leaf_max; }, 1, kLeafMax, 1, false, "rt_set_tuning: leaf max must be in [1, 4]"},
+    {[]() -> int& { return g_persistent_waves; }, 0, 16, 1, false,
+     "rt_set_tuning: persistent waves per SIMD must be in [0, 16]"},
+    {[]() -> int& { return g_sah_traversal_x10; }, 1, 1000, 1, false,
+     "rt_set_tuning: SAH traversal cost (x10) must be in [1, 1000]"},
+    {[]() -> int& { return g_lds_pad; }, 0, 65536, 4, false, "rt_set_tuning: LDS pad must be a multiple of 4 in [0, 65536]"},
+    {[]() -> int& { return g_adaptive_order; }, 0, 1, 1, false, "rt_set_tuning: adaptive order must be 0 or 1"},
+    {[]() -> int& { return g_texel_bytes; }, 3, 4, 1, false, "rt_set_tuning: texel layout must be 3 (RGB8) or 4 (RGBA8)"},
+    {[]() -> int& { return g_queue_chunk; }, 64, 4096, 64, false,
+     "rt_set_tuning: queue chunk must be a multiple of 64 in [64, 4096]"},
+    {[]() -> int& { return g_queue_stride; }, 128, (int)kQueueMaxStride, 1, true,
+     "rt_set_tuning: queue head stride must be a power of two in [128, 4096] bytes"},
+    {[]() -> int& { return g_regen_live_frac; }, 0, 64, 1, false, "rt_set_tuning: live fraction must be in [0, 64]"},
+    {[]() -> int& { return g_leaf_break; }, 0, 64, 1, false, "rt_set_tuning: leaf break must be in [0, 64]"},
+    {[]() -> int& { return g_rius_trips; }, 0, 64, 1, false, "rt_set_tuning: RandomInUnitSphere trips must be in [0, 64]"},
+    {[]() -> int& { return g_flat_max; }, 0, (int)kFlatMaxPrims, 1, false,
+     "rt_set_tuning: flat kernel primitive limit must be in [0, 64]"},
+    {[]() -> int& { return g_queue_prefetch; }, 0, 64, 1, false, "rt_set_tuning: queue prefetch must be in [0, 64]"},
+    {[]() -> int& { return g_queue_guide; }, 0, 64, 1, false, "rt_set_tuning: queue guide factor must be in [0, 64]"},
+    {[]() -> int& { return g_queue_min; }, 16, 64, 16, false, "rt_set_tuning: guided chunk floor must be 16, 32, 48 or 64"},
+    {[]() -> int& { return g_rius_trips_persistent; }, 0, 64, 1, false,
+     "rt_set_tuning: RandomInUnitSphere trips must be in [0, 64]"},
+    {[]() -> int& { return g_prefetch_stop; }, 0, 1024, 1, false, "rt_set_tuning: prefetch stop must be in [0, 1024]"},
+    {[]() -> int& { return g_persistent_group; }, 0, 2, 1, false, "rt_set_tuning: persistent group must be 0, 1 or 2"},
+    {[]() -> int& { return g_group_tail; }, 0, 1000, 1, false, "rt_set_tuning: group tail must be in [0, 1000] permille"},
+    {[]() -> int& { return g_group_order; }, 0, 1, 1, false, "rt_set_tuning: group order must be 0 or 1"},
+    {[]() -> int& { return g_queue_host_reset; }, 0, 1, 1, false, "rt_set_tuning: queue reset must be 0 or 1"},
+    {[]() -> int& { return g_group_chunk; }, 64, 4096, 64, false,
+     "rt_set_tuning: group chunk must be a multiple of 64 in [64, 4096]"},
+    {[]() -> int& { return g_group_linger_us; }, 0, 100000, 1, false,
+     "rt_set_tuning: group linger must be in [0, 100000] us"},
+    {[]() -> int& { return g_group_waves; }, 4, 16, 4, false, "rt_set_tuning: group waves must be 4, 8, 12 or 16"},
+    {[]() -> int& { return g_tile_entries; }, 0, 1, 1, false, "rt_set_tuning: tile entries must be 0 or 1"},
+    {[]() -> int& { return g_camera_resolve; }, 0, kCameraResolveMax, 1, false,
+     "rt_set_tuning: camera resolve must be 0, 1 or a primitive cap in [2, 32]"},
+    {[]() -> int& { return g_path_end_step; }, 0, 1, 1, false, "rt_set_tuning: path end step must be 0 or 1"},
+};
+static_assert(sizeof(kKnobs) / sizeof(kKnobs[0]) == RT_TUNE_PATH_END_STEP + 1, "one row per rt_tuning_key");
+
 int hip_check(hipError_t e, const char* what, int code = RT_ERR_DEVICE) {
     if (e == hipSuccess) return RT_OK;
     set_error(std::string(what) + ": " + hipGetErrorString(e));
@@ -4013,22 +4131,6 @@ constexpr int kPhiloxCompactWaves = 8;  // ... of the non-texture Philox build o
 
 constexpr int kFlatWaves = 8;  // __launch_bounds__ waves per SIMD of the untextured flat kernel
 constexpr int kFlatPersistentWaves = 4;  // resident waves per SIMD of the persistent flat kernel's grid
-// RT_TUNE_PERSISTENT_GROUP: the persistent flat kernel's 16-wave workgroups drawing chunks from the queue heads (2,
-// default: GroupQueue), with static tile shares (1: GroupShare), or the round-5 one-wave workgroups on the per-wave
-// queue alone (0); profiles/r06b_ab_c5_group_shares.txt
-thread_local int g_persistent_group = 2;
-// RT_TUNE_GROUP_TAIL: permille of the frame's tiles left to the per-wave queue behind the groups' static shares
-thread_local int g_group_tail = 0;
-// RT_TUNE_GROUP_ORDER: the shares' tiles interleaved (0: tile g + k·groups) or in golden-ratio order (1)
-thread_local int g_group_order = 0;
-// RT_TUNE_GROUP_CHUNK: positions per chunk of the workgroup chunk queue (RT_TUNE_PERSISTENT_GROUP 2)
-thread_local int g_group_chunk = 1024;
-// RT_TUNE_GROUP_WAVES: waves per workgroup of the GROUP builds (4, 8, 12 or 16)
-thread_local int g_group_waves = 16;
-// RT_TUNE_GROUP_LINGER_US: a finished workgroup waits up to this long for the grid's others before it exits (0: off)
-thread_local int g_group_linger_us = 0;
-// RT_TUNE_QUEUE_RESET: 1 = rt_render zeroes the persistent kernels' queue slot per launch (and they skip queue_release)
-thread_local int g_queue_host_reset = 0;
 template <bool PH, int G>
 KernelFn flat_persistent_pick(bool count, bool tex, bool trace) {
     if (tex)
@@ -4053,7 +4155,7 @@ KernelFn pick(int variant, bool count, bool tex, bool philox, bool wide, bool tr
     if (variant == kVarFlat || variant == kVarFlatPersistent)
         return philox ? flat_pick<true>(count, tex, variant == kVarFlatPersistent, trace)
                       : flat_pick<false>(count, tex, variant == kVarFlatPersistent, trace);
-    if (wide) {  // 32-bit references: builds of the compact v3 and of v4 only (rt_render maps wide scenes there)
+    if (wide) {  // 32-bit references: builds of the compact v3 and of v4 only (resolve_variant maps wide scenes there)
         if (variant == kVarV3Compact)
             return philox ? v3_pick<1, true, true, true>(count, tex) : v3_pick<1, false, true, true>(count, tex);
         return philox ? v4_pick<true, true>(count, tex, trace) : v4_pick<false, true>(count, tex, trace);
@@ -4074,10 +4176,6 @@ KernelFn pick(int variant, bool count, bool tex, bool philox, bool wide, bool tr
     }
 }
 
-// RT_TUNE_REGEN_THRESHOLD: 56 together with the live-pixel cap below (the pair's plateau, 56-64 x 52-60/64, is
-// flat within 0.3 %; 40 without the cap was round 2's optimum: profiles/r03o_sweep_regen_live_frac.txt)
-thread_local int g_regen_threshold = 56;
-thread_local int g_lds_pad = 0;  // diagnostic: extra LDS bytes per wave (occupancy experiments)
 thread_local unsigned long long* g_wave_trace = nullptr;  // diagnostic: rt_set_wave_trace
 thread_local unsigned long long g_wave_trace_words = 0;
 thread_local uint8_t* g_pixel_cost = nullptr;  // diagnostic: rt_set_pixel_cost
@@ -4086,29 +4184,6 @@ thread_local uint32_t* g_ray_dump_count = nullptr;
 thread_local uint32_t g_ray_dump_cap = 0, g_ray_dump_depth = 1;
 thread_local uint64_t g_pixel_cost_bytes = 0;
 thread_local const uint32_t* g_tile_order = nullptr;       // experiment: rt_set_tile_order
-thread_local int g_adaptive_order = 1;                      // RT_TUNE_ADAPTIVE_ORDER
-// RT_TUNE_REGEN_LIVE_FRAC: v3's regeneration threshold is capped at 48/64 of the wave's live pixels, so a wave whose
-// pixels are finishing keeps tracing until most of its remaining lanes are done instead of shading a few lanes per
-// leaf pass; with it a higher base threshold pays (C2 −2.1 % for the pair against 40 without the cap, C4 −2.4 %,
-// C3 ±0.2 %: profiles/r03o_sweep_regen_live_frac.txt; 48 rather than 56 once the leaf-break rule is on, −0.6 %:
-// profiles/r03s_ab_node_min_cap.txt)
-thread_local int g_regen_live_frac = 48;
-// RT_TUNE_LEAF_BREAK: leave the node loop for the leaf tests once at most 3 traversing lanes still lack a leaf
-// (with the threshold pair above: C2 −2.4 %, C4 −3.5 %, C3 ±0; round 2 measured −1.2 / +1 % at 2 with threshold 40
-// and no cap: profiles/r03r_ab_leaf_break.txt)
-thread_local int g_leaf_break = 3;
-// RT_TUNE_FLAT_MAX: scenes of at most this many primitives run the flat kernels (variants 5, 6) where the automatic
-// choice would run v3 / v4.  RT_TUNE_RIUS_TRIPS: the tile flat kernel's RandomInUnitSphere attempts per pass before a
-// rejecting lane defers the rest of the call to the next pass (0 = unbounded; 4: C3's optimum, a wave otherwise runs
-// the loop as long as its unluckiest lane).  RT_TUNE_RIUS_TRIPS_PERSISTENT: the same for the persistent flat kernel,
-// unbounded by default — a C5 frame is bound by its last pixels' chains of passes, and a deferred call adds a pass to
-// one (C5 0.262 -> 0.253 ms per step unbounded, K = 4 / 6 / 8: 0.262 / 0.260 / 0.255; profiles/r05u_c5_rius_trips.txt)
-thread_local int g_flat_max = 16;
-thread_local int g_rius_trips = 4;
-thread_local int g_rius_trips_persistent = 0;
-// RT_TUNE_PREFETCH_STOP: the persistent flat kernel's lanes take their next pixel ahead (kFlatPrefetch) only while their
-// wave's queue head holds more than 1/value of its range (0 = never); kPrefetchStop (8) by default
-thread_local int g_prefetch_stop = (int)dev::kPrefetchStop;
 
 // Per (device, stream, tile grid): the tile costs the v3 kernel records and the order planned from them.
 // Plans are held by shared_ptr: a caller keeps its plan alive across the launch even if another thread
@@ -4194,20 +4269,6 @@ int acquire_plan(const PlanKey& key, hipStream_t s, std::shared_ptr<TilePlan>* o
     *out = it->second;
     return RT_OK;
 }
-// RT_TUNE_TILE_ENTRIES: 1 (default) = the v3 kernels start a full tile's camera rays at the tile's candidate leaves
-// (rt_tile_entry.h; 16-bit-reference scenes, band_rows a multiple of 8), 0 = every ray starts at the root (A/B, tests)
-thread_local int g_tile_entries = 1;
-// RT_TUNE_CAMERA_RESOLVE: 1 (default) = with the entry records, a v3 shading pass ends its cleared misses ahead of
-// shade() and resolves their next camera rays by a scan of the tile's record (v3_resolve_camera), for records of at
-// most kCameraResolveCap primitives; 2..32 = the same with that cap (A/B, tests); 0 = off: every camera ray takes the
-// leaf chain (the parent's behaviour)
-thread_local int g_camera_resolve = 1;
-constexpr uint32_t kCameraResolveCap = 8;
-constexpr int kCameraResolveMax = 32;  // a record's eight references hold at most four primitives each
-// RT_TUNE_PATH_END_STEP: 1 (default) = where the pre-step scans a wave's record, every path end of the wave (absorption,
-// the depth limit, an emitter, a camera ray that missed) and the pixel's first camera ray go through the pre-step too:
-// no lane holds a camera ray's leaf chain through a traversal call; 0 = only cleared misses do (A/B, tests)
-thread_local int g_path_end_step = 1;
 
 // Per (device, stream, tile grid): the tiles' entry records and what they were filled for.  The pre-pass runs again
 // only when the scene, the camera terms, the frame shape or the band layout differ from the launch that filled the
@@ -4278,8 +4339,6 @@ TileFrame tile_frame_of(const dev::KParams& P, const bool wide_refs, const uint3
     return F;
 }
 
-thread_local int g_persistent_waves = 0;  // 0: occupancy query
-
 constexpr size_t kLdsLimit = 160 * 1024;
 constexpr size_t kFlatTabLdsMax = 16 * 1024;  // LDS per persistent flat wave for the scene tables (64 primitives: 4 KB)
 
@@ -4288,15 +4347,6 @@ constexpr size_t kFlatTabLdsMax = 16 * 1024;  // LDS per persistent flat wave fo
 // plus the exhausted-heads word) and is reused after kQueueSlots further persistent launches on that device:
 // a caller may keep at most kQueueSlots persistent launches in flight per device (rt_hip.h, rt_render).
 constexpr uint32_t kQueueSlots = 256;
-constexpr uint32_t kQueueMaxStride = 4096;  // bytes between heads (RT_TUNE_QUEUE_STRIDE)
-thread_local int g_queue_stride = 128;  // RT_TUNE_QUEUE_STRIDE: bytes between the v4 kernel's queue heads
-// RT_TUNE_QUEUE_CHUNK: work indices per queue atomic while the head has plenty left.  128 since the texel gather
-// overlaps RandomInUnitSphere: C5 -3.6 % against 64 (0.2525 vs 0.2620 ms, 6 alternations; 192 / 256 lose,
-// profiles/r05ag_c5_queue_chunk.txt); round 3 had measured 64..256 within 3 %
-thread_local int g_queue_chunk = 128;
-thread_local int g_queue_prefetch = 32; // RT_TUNE_QUEUE_PREFETCH: fetch the next chunk ahead at this many indices left
-thread_local int g_queue_guide = 0;     // RT_TUNE_QUEUE_GUIDE: guided chunks, head_left / (waves per head × this)
-thread_local int g_queue_min = 16;      // RT_TUNE_QUEUE_MIN_CHUNK: the guided chunks' floor
 constexpr int kMaxDevices = 64;
 struct QueueRing {
     uint32_t* buf = nullptr;
@@ -4351,7 +4401,112 @@ int acquire_queue(int device, uint32_t stride, uint32_t** head, int* cus) {
     return RT_OK;
 }
 
+// ----- pieces the entry points share --------------------------------------------------------------------
+
+bool tiling_ok(const rt_tiling& T) { return T.band_rows != 0 && T.num_ranks != 0 && T.rank < T.num_ranks; }
+
+int check_tiling(const char* who, const rt_tiling& T) {
+    if (tiling_ok(T)) return RT_OK;
+    set_error(std::string(who) + ": invalid tiling");
+    return RT_ERR_INVALID_ARGUMENT;
+}
+
+// the last local row must map into the image (T checked, local_rows > 0)
+int check_last_row(const char* who, const rt_tiling& T, const uint32_t height) {
+    const uint32_t l = T.local_rows - 1, band = l / T.band_rows, within = l % T.band_rows;
+    const uint64_t g = ((uint64_t)band * T.num_ranks + T.rank) * T.band_rows + within;
+    if (g < height) return RT_OK;
+    set_error(std::string(who) + ": tiling maps local rows outside the image");
+    return RT_ERR_INVALID_ARGUMENT;
+}
+
+// The frame and this rank's bands of it; faithful (RT_FLAG_FAITHFUL_GRID): the reference's grid of whole 16×16 blocks.
+void fill_frame(dev::KParams& P, const uint32_t width, const uint32_t height, const rt_tiling& T, const bool faithful) {
+    P.width = width;
+    P.height = height;
+    P.band_rows = T.band_rows;
+    P.num_ranks = T.num_ranks;
+    P.rank = T.rank;
+    P.local_rows = T.local_rows;
+    P.grid_w = faithful ? (width / 16) * 16 : width;
+    P.grid_h = faithful ? (height / 16) * 16 : height;
+}
+
+// The scene's BVH-order tables (a kernel reads the ones it needs)
+void fill_scene_tables(dev::KParams& P, const DeviceScene& S) {
+    P.nodes = (const float4*)S.nodes;
+    P.nodes48 = (const float4*)S.nodes48;
+    P.refs = (const uint32_t*)S.refs;
+    P.prims = (const float4*)S.prims;
+    P.mats = (const float4*)S.mats;
+    P.imgs = (const int4*)S.imgs;
+    P.texels = (const uint8_t*)S.texels;
+    P.num_nodes = S.num_nodes;
+    P.num_prims = S.num_prims;
+    P.num_mats = S.num_mats;
+    P.num_imgs = S.num_imgs;
+}
+
+// ... and for the flat kernels, in the BVH tables' place: the primitives in the reference's test order, its BVH
+void fill_flat_tables(dev::KParams& P, const DeviceScene& S) {
+    P.prims = (const float4*)S.prims_flat;
+    P.ref_nodes = (const float4*)S.ref_nodes;
+    P.flat_ref_pairs = (const float4*)S.flat_ref_pairs;
+    P.flat_boxes = (const float4*)S.flat_boxes;
+    P.flat_runs[0] = S.flat_runs[0];
+    P.flat_runs[1] = S.flat_runs[1];
+}
+
+int tile_kernel_of(const bool flat) { return flat ? kVarFlat : kVarV3Compact; }
+int persistent_kernel_of(const bool flat) { return flat ? kVarFlatPersistent : kVarV4; }
+
 }  // namespace
+
+// The automatic choice before any measurement: the fastest measured kernel per workload shape (profiles/r01d_*,
+// r01e_*): the persistent v4 when a pixel has few paths (config 5: 1 spp, 0.51-0.54 vs 0.80 ms), otherwise v3 with the
+// adaptive longest-first tile order and compact parking: 13 words of parked state + a depth + 2 stack fit config 2's
+// wave in 5 KB of LDS, 8 waves per SIMD (config 2: 17.05 vs 17.8 ms with 15-word parking; config 3, depth 16: 365 vs
+// 408 ms for v4).  Small scenes: the flat kernels take their places.  (Until round 5 also scenes of up to kFlatMaxPrims
+// primitives whose rectangles touch others, where only the flat kernels were exact; the BVH kernels now replay the
+// reference traversal where it could differ, bvh_clear, and are faster beyond 16.)
+int static_variant(const uint32_t spp, const bool prims_flat, const uint32_t num_prims, const uint32_t flat_max) {
+    const bool flat = prims_flat && num_prims <= flat_max;
+    return spp < 32 ? persistent_kernel_of(flat) : tile_kernel_of(flat);
+}
+
+// What a requested variant becomes on this scene and frame; the order of the rules is part of the contract.
+VariantChoice resolve_variant(int variant, const VariantFacts& f) {
+    const bool packable = f.spp < 8192u && f.max_depth < 64u && (uint64_t)f.spp * f.max_depth < 8192u;
+    const int v3 = packable ? kVarV3Compact : kVarV3;  // compact parking falls back to 15 words where its packed
+                                                       // counters would overflow
+    if (variant == kVarFlat && !f.prims_flat) variant = kVarV3Compact;  // (a scene beyond kFlatMaxPrims)
+    // the persistent flat kernel stages the flat tables in LDS: a scene whose materials overflow kFlatTabLdsMax runs v4
+    if (variant == kVarFlatPersistent && (!f.prims_flat || f.flat_tab_bytes > kFlatTabLdsMax)) variant = kVarV4;
+    if (kVariants[variant].compact && !packable) variant = kVarV3;
+    if ((kVariants[variant].kernel == 4 || kVariants[variant].kernel == 6) && (f.spp == 0 || f.max_depth == 0))
+        variant = kVariants[variant].kernel == 6 ? kVarFlat : v3;  // the persistent kernels assume every pixel traces a ray
+    if (f.philox && kVariants[variant].stack != dev::STACK_LDS16 && kVariants[variant].stack != dev::STACK_NONE)
+        variant = v3;  // the v1/v2 kernels have no Philox build
+    // Scenes whose references need 32 bits (wide_refs: >= 32767 nodes or >= 8192 primitives) run the WIDE builds
+    // of the compact v3 and of v4; the 15-word v3 has none: v2 / v1 there (no Philox build either).
+    bool wide = false;
+    if (kVariants[variant].stack == dev::STACK_LDS16 && f.wide_refs) {
+        if (variant != kVarV3) {
+            wide = true;
+        } else if (f.philox) {
+            return {variant, false, RT_ERR_UNSUPPORTED,
+                    "rt_render: RT_FLAG_RNG_PHILOX on a scene with 32-bit references needs spp < 8192, "
+                    "max_depth < 64 and spp * max_depth < 8192"};
+        } else {
+            variant = f.bvh_depth <= 25u ? kVarV2 : kVarV1;  // 32-bit LDS stacks, or scratch if deep
+        }
+    }
+    // near-first traversal holds at most one deferred child per level below the root
+    if (kVariants[variant].stack == dev::STACK_LDS && f.bvh_depth > (uint32_t)kVariants[variant].lds_depth + 1)
+        return {variant, false, RT_ERR_UNSUPPORTED,
+                "rt_render: BVH too deep for the LDS stack of kernel variant " + std::to_string(variant)};
+    return {variant, wide, RT_OK, std::string()};
+}
 
 }  // namespace rt
 
@@ -4431,7 +4586,7 @@ int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* input
         set_error("rt_tile_entries_host: NULL argument");
         return RT_ERR_INVALID_ARGUMENT;
     }
-    if (tiling->band_rows == 0 || tiling->num_ranks == 0 || tiling->rank >= tiling->num_ranks || width == 0 || height == 0) {
+    if (!tiling_ok(*tiling) || width == 0 || height == 0) {
         set_error("rt_tile_entries_host: invalid frame or tiling");
         return RT_ERR_INVALID_ARGUMENT;
     }
@@ -4451,15 +4606,7 @@ int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* input
     std::memset(&P, 0, sizeof(P));
     P.num_nodes = h.num_nodes;
     P.num_prims = h.num_prims;
-    P.width = width;
-    P.height = height;
-    P.band_rows = tiling->band_rows;
-    P.num_ranks = tiling->num_ranks;
-    P.rank = tiling->rank;
-    P.local_rows = tiling->local_rows;
-    const bool faithful = (flags & RT_FLAG_FAITHFUL_GRID) != 0;
-    P.grid_w = faithful ? (width / 16) * 16 : width;
-    P.grid_h = faithful ? (height / 16) * 16 : height;
+    fill_frame(P, width, height, *tiling, (flags & RT_FLAG_FAITHFUL_GRID) != 0);
     P.tiles_x = (width + 7u) / 8u;
     fill_camera(P, *inputs, width, height);
     const uint64_t tiles = (uint64_t)P.tiles_x * ((tiling->local_rows + 7u) / 8u);
@@ -4485,11 +4632,7 @@ int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t*
     if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_trace_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
     dev::KParams P;
     std::memset(&P, 0, sizeof(P));
-    P.nodes48 = (const float4*)S.nodes48;
-    P.refs = (const uint32_t*)S.refs;
-    P.prims = (const float4*)S.prims;
-    P.num_nodes = S.num_nodes;
-    P.num_prims = S.num_prims;
+    fill_scene_tables(P, S);
     P.counters = (unsigned long long*)counters;
     P.regen_threshold = (uint32_t)g_regen_threshold;
     P.regen_live_frac = (uint32_t)g_regen_live_frac;
@@ -4517,16 +4660,9 @@ int rt_gbuffer(const rt_scene* scene, const rt_gbuffer_args* a, rt_stream stream
     if (!scene) { set_error("rt_gbuffer: NULL scene"); return RT_ERR_INVALID_ARGUMENT; }
     const rt_tiling& T = a->tiling;
     if (a->width == 0 || a->height == 0 || T.local_rows == 0) return RT_OK;  // nothing to trace
-    if (T.band_rows == 0 || T.num_ranks == 0 || T.rank >= T.num_ranks) {
-        set_error("rt_gbuffer: invalid tiling");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    {
-        // the last local row must map into the image
-        uint32_t l = T.local_rows - 1, band = l / T.band_rows, within = l % T.band_rows;
-        uint64_t g = ((uint64_t)band * T.num_ranks + T.rank) * T.band_rows + within;
-        if (g >= a->height) { set_error("rt_gbuffer: tiling maps local rows outside the image"); return RT_ERR_INVALID_ARGUMENT; }
-    }
+    int rc = check_tiling("rt_gbuffer", T);
+    if (rc == RT_OK) rc = check_last_row("rt_gbuffer", T, a->height);
+    if (rc != RT_OK) return rc;
     const DeviceScene& S = scene->dev;
     if (S.wide_refs) { set_error("rt_gbuffer: scenes with 32-bit references are not supported"); return RT_ERR_UNSUPPORTED; }
     // the scenes rt_render's automatic choice gives to the flat kernels
@@ -4536,31 +4672,10 @@ int rt_gbuffer(const rt_scene* scene, const rt_gbuffer_args* a, rt_stream stream
     dev::GBufParams G;
     std::memset(&G, 0, sizeof(G));
     dev::KParams& P = G.K;
-    P.nodes48 = (const float4*)S.nodes48;
-    P.refs = (const uint32_t*)S.refs;
-    P.prims = (const float4*)(flat ? S.prims_flat : S.prims);
-    P.mats = (const float4*)S.mats;
-    P.imgs = (const int4*)S.imgs;
-    P.texels = (const uint8_t*)S.texels;
-    P.num_nodes = S.num_nodes;
-    P.num_prims = S.num_prims;
-    P.num_mats = S.num_mats;
-    P.num_imgs = S.num_imgs;
-    P.width = a->width;
-    P.height = a->height;
-    P.band_rows = T.band_rows;
-    P.num_ranks = T.num_ranks;
-    P.rank = T.rank;
-    P.local_rows = T.local_rows;
-    P.grid_w = a->width;
-    P.grid_h = a->height;
+    fill_scene_tables(P, S);
+    if (flat) fill_flat_tables(P, S);
+    fill_frame(P, a->width, a->height, T, false);
     P.leaf_break = (uint32_t)g_leaf_break;
-    if (flat) {
-        P.ref_nodes = (const float4*)S.ref_nodes;
-        P.flat_boxes = (const float4*)S.flat_boxes;
-        P.flat_runs[0] = S.flat_runs[0];
-        P.flat_runs[1] = S.flat_runs[1];
-    }
     fill_camera(P, a->inputs, a->width, a->height);
     P.tiles_x = (a->width + 7u) / 8u;
     const uint64_t tiles = (uint64_t)P.tiles_x * ((T.local_rows + 7u) / 8u);
@@ -4608,336 +4723,84 @@ int rt_set_variant(int variant) {
 int rt_last_variant(void) { return g_last_variant; }
 
 int rt_set_tuning(int key, int value) {
-    if (key == RT_TUNE_REGEN_THRESHOLD) {
-        if (value < 1 || value > 64) {
-            set_error("rt_set_tuning: regen threshold must be in [1, 64]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_regen_threshold;
-        g_regen_threshold = value;
-        return prev;
+    if (key < 0 || key >= (int)(sizeof(kKnobs) / sizeof(kKnobs[0]))) {
+        set_error("rt_set_tuning: unknown key");
+        return RT_ERR_INVALID_ARGUMENT;
     }
-    if (key == RT_TUNE_LEAF_MAX) {
-        if (value < 1 || value > kLeafMax) {
-            set_error("rt_set_tuning: leaf max must be in [1, 4]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_leaf_max;
-        g_leaf_max = value;
-        return prev;
+    const Knob& k = kKnobs[key];
+    if (value < k.lo || value > k.hi || value % k.step || (k.pow2 && (value & (value - 1)))) {
+        set_error(k.refusal);
+        return RT_ERR_INVALID_ARGUMENT;
     }
-    if (key == RT_TUNE_SAH_TRAVERSAL) {
-        if (value < 1 || value > 1000) {
-            set_error("rt_set_tuning: SAH traversal cost (x10) must be in [1, 1000]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_sah_traversal_x10;
-        g_sah_traversal_x10 = value;
-        return prev;
-    }
-    if (key == RT_TUNE_ADAPTIVE_ORDER) {
-        if (value < 0 || value > 1) {
-            set_error("rt_set_tuning: adaptive order must be 0 or 1");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_adaptive_order;
-        g_adaptive_order = value;
-        return prev;
-    }
-    if (key == RT_TUNE_TEXEL_LAYOUT) {
-        if (value != 3 && value != 4) {
-            set_error("rt_set_tuning: texel layout must be 3 (RGB8) or 4 (RGBA8)");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_texel_bytes;
-        g_texel_bytes = value;
-        return prev;
-    }
-    if (key == RT_TUNE_LDS_PAD) {
-        if (value < 0 || value > 65536 || value % 4) {
-            set_error("rt_set_tuning: LDS pad must be a multiple of 4 in [0, 65536]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_lds_pad;
-        g_lds_pad = value;
-        return prev;
-    }
-    if (key == RT_TUNE_QUEUE_CHUNK) {
-        if (value < 64 || value > 4096 || value % 64) {
-            set_error("rt_set_tuning: queue chunk must be a multiple of 64 in [64, 4096]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_queue_chunk;
-        g_queue_chunk = value;
-        return prev;
-    }
-    if (key == RT_TUNE_QUEUE_STRIDE) {
-        if (value < 128 || value > (int)kQueueMaxStride || (value & (value - 1))) {
-            set_error("rt_set_tuning: queue head stride must be a power of two in [128, 4096] bytes");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_queue_stride;
-        g_queue_stride = value;
-        return prev;
-    }
-    if (key == RT_TUNE_REGEN_LIVE_FRAC) {
-        if (value < 0 || value > 64) {
-            set_error("rt_set_tuning: live fraction must be in [0, 64]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_regen_live_frac;
-        g_regen_live_frac = value;
-        return prev;
-    }
-    if (key == RT_TUNE_LEAF_BREAK) {
-        if (value < 0 || value > 64) {
-            set_error("rt_set_tuning: leaf break must be in [0, 64]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_leaf_break;
-        g_leaf_break = value;
-        return prev;
-    }
-    if (key == RT_TUNE_RIUS_TRIPS || key == RT_TUNE_RIUS_TRIPS_PERSISTENT) {
-        if (value < 0 || value > 64) {
-            set_error("rt_set_tuning: RandomInUnitSphere trips must be in [0, 64]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int& knob = key == RT_TUNE_RIUS_TRIPS ? g_rius_trips : g_rius_trips_persistent;
-        int prev = knob;
-        knob = value;
-        return prev;
-    }
-    if (key == RT_TUNE_PREFETCH_STOP) {
-        if (value < 0 || value > 1024) {
-            set_error("rt_set_tuning: prefetch stop must be in [0, 1024]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_prefetch_stop;
-        g_prefetch_stop = value;
-        return prev;
-    }
-    if (key == RT_TUNE_GROUP_WAVES) {
-        if (value < 4 || value > 16 || value % 4) {
-            set_error("rt_set_tuning: group waves must be 4, 8, 12 or 16");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_group_waves;
-        g_group_waves = value;
-        return prev;
-    }
-    if (key == RT_TUNE_GROUP_LINGER_US) {
-        if (value < 0 || value > 100000) {
-            set_error("rt_set_tuning: group linger must be in [0, 100000] us");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_group_linger_us;
-        g_group_linger_us = value;
-        return prev;
-    }
-    if (key == RT_TUNE_GROUP_CHUNK) {
-        if (value < 64 || value > 4096 || value % 64) {
-            set_error("rt_set_tuning: group chunk must be a multiple of 64 in [64, 4096]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_group_chunk;
-        g_group_chunk = value;
-        return prev;
-    }
-    if (key == RT_TUNE_PERSISTENT_GROUP) {
-        if (value < 0 || value > 2) {
-            set_error("rt_set_tuning: persistent group must be 0, 1 or 2");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_persistent_group;
-        g_persistent_group = value;
-        return prev;
-    }
-    if (key == RT_TUNE_QUEUE_RESET) {
-        if (value < 0 || value > 1) {
-            set_error("rt_set_tuning: queue reset must be 0 or 1");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_queue_host_reset;
-        g_queue_host_reset = value;
-        return prev;
-    }
-    if (key == RT_TUNE_GROUP_ORDER) {
-        if (value < 0 || value > 1) {
-            set_error("rt_set_tuning: group order must be 0 or 1");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_group_order;
-        g_group_order = value;
-        return prev;
-    }
-    if (key == RT_TUNE_GROUP_TAIL) {
-        if (value < 0 || value > 1000) {
-            set_error("rt_set_tuning: group tail must be in [0, 1000] permille");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_group_tail;
-        g_group_tail = value;
-        return prev;
-    }
-    if (key == RT_TUNE_FLAT_MAX) {
-        if (value < 0 || value > (int)kFlatMaxPrims) {
-            set_error("rt_set_tuning: flat kernel primitive limit must be in [0, 64]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_flat_max;
-        g_flat_max = value;
-        return prev;
-    }
-    if (key == RT_TUNE_QUEUE_GUIDE) {
-        if (value < 0 || value > 64) {
-            set_error("rt_set_tuning: queue guide factor must be in [0, 64]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_queue_guide;
-        g_queue_guide = value;
-        return prev;
-    }
-    if (key == RT_TUNE_QUEUE_MIN_CHUNK) {
-        if (value < 16 || value > 64 || value % 16) {
-            set_error("rt_set_tuning: guided chunk floor must be 16, 32, 48 or 64");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_queue_min;
-        g_queue_min = value;
-        return prev;
-    }
-    if (key == RT_TUNE_QUEUE_PREFETCH) {
-        if (value < 0 || value > 64) {
-            set_error("rt_set_tuning: queue prefetch must be in [0, 64]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_queue_prefetch;
-        g_queue_prefetch = value;
-        return prev;
-    }
-    if (key == RT_TUNE_PERSISTENT_WAVES) {
-        if (value < 0 || value > 16) {
-            set_error("rt_set_tuning: persistent waves per SIMD must be in [0, 16]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_persistent_waves;
-        g_persistent_waves = value;
-        return prev;
-    }
-    if (key == RT_TUNE_TILE_ENTRIES) {
-        if (value < 0 || value > 1) {
-            set_error("rt_set_tuning: tile entries must be 0 or 1");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_tile_entries;
-        g_tile_entries = value;
-        return prev;
-    }
-    if (key == RT_TUNE_CAMERA_RESOLVE) {
-        if (value < 0 || value > kCameraResolveMax) {
-            set_error("rt_set_tuning: camera resolve must be 0, 1 or a primitive cap in [2, 32]");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_camera_resolve;
-        g_camera_resolve = value;
-        return prev;
-    }
-    if (key == RT_TUNE_PATH_END_STEP) {
-        if (value < 0 || value > 1) {
-            set_error("rt_set_tuning: path end step must be 0 or 1");
-            return RT_ERR_INVALID_ARGUMENT;
-        }
-        int prev = g_path_end_step;
-        g_path_end_step = value;
-        return prev;
-    }
-    set_error("rt_set_tuning: unknown key");
-    return RT_ERR_INVALID_ARGUMENT;
+    int& knob = k.at();
+    const int prev = knob;
+    knob = value;
+    return prev;
 }
 
-int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) {
-    if (!scene || !a) { set_error("rt_render: NULL scene or args"); return RT_ERR_INVALID_ARGUMENT; }
-    if (a->tiling.local_rows == 0 || a->width == 0 || a->height == 0) return RT_OK;  // nothing to render
-    const bool philox = (a->flags & RT_FLAG_RNG_PHILOX) != 0;
-    if (!a->state && !philox) { set_error("rt_render: state is NULL"); return RT_ERR_INVALID_ARGUMENT; }
-    if (philox && a->samples_per_pixel > RT_PHILOX_MAX_SPP) {  // sample s reads the window at word s << 18
-        set_error("rt_render: RT_FLAG_RNG_PHILOX supports at most RT_PHILOX_MAX_SPP (16384) samples per pixel");
+// ----- rt_render, step by step --------------------------------------------------------------------------
+namespace {
+
+// The arguments of a frame that has pixels to render
+int check_render_args(const rt_scene& scene, const rt_render_args& a) {
+    const auto refuse = [](const char* what) -> int {
+        set_error(what);
         return RT_ERR_INVALID_ARGUMENT;
-    }
-    if (a->reserved != 0 || a->reserved2 != 0) { set_error("rt_render: reserved fields must be 0"); return RT_ERR_INVALID_ARGUMENT; }
-    if (!a->pos && !a->radiance && !a->accum) { set_error("rt_render: no output buffer"); return RT_ERR_INVALID_ARGUMENT; }
-    if ((a->flags & RT_FLAG_ACCUMULATE) && !a->accum) { set_error("rt_render: ACCUMULATE without accum"); return RT_ERR_INVALID_ARGUMENT; }
-    if ((a->flags & RT_FLAG_ACCUMULATE_RESET) && !(a->flags & RT_FLAG_ACCUMULATE)) {
-        set_error("rt_render: ACCUMULATE_RESET without ACCUMULATE");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    if (a->width == 0 || a->height == 0) return RT_OK;
-    const rt_tiling& T = a->tiling;
-    if (T.band_rows == 0 || T.num_ranks == 0 || T.rank >= T.num_ranks) {
-        set_error("rt_render: invalid tiling");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
-    if (T.local_rows == 0) return RT_OK;
-    {
-        // the last local row must map into the image
-        uint32_t l = T.local_rows - 1, band = l / T.band_rows, within = l % T.band_rows;
-        uint64_t g = ((uint64_t)band * T.num_ranks + T.rank) * T.band_rows + within;
-        if (g >= a->height) { set_error("rt_render: tiling maps local rows outside the image"); return RT_ERR_INVALID_ARGUMENT; }
-    }
-    const DeviceScene& S = scene->dev;
-    if (S.depth > (uint32_t)dev::kStackMax) {
+    };
+    const bool philox = (a.flags & RT_FLAG_RNG_PHILOX) != 0;
+    if (!a.state && !philox) return refuse("rt_render: state is NULL");
+    if (philox && a.samples_per_pixel > RT_PHILOX_MAX_SPP)  // sample s reads the window at word s << 18
+        return refuse("rt_render: RT_FLAG_RNG_PHILOX supports at most RT_PHILOX_MAX_SPP (16384) samples per pixel");
+    if (a.reserved != 0 || a.reserved2 != 0) return refuse("rt_render: reserved fields must be 0");
+    if (!a.pos && !a.radiance && !a.accum) return refuse("rt_render: no output buffer");
+    if ((a.flags & RT_FLAG_ACCUMULATE) && !a.accum) return refuse("rt_render: ACCUMULATE without accum");
+    if ((a.flags & RT_FLAG_ACCUMULATE_RESET) && !(a.flags & RT_FLAG_ACCUMULATE))
+        return refuse("rt_render: ACCUMULATE_RESET without ACCUMULATE");
+    int rc = check_tiling("rt_render", a.tiling);
+    if (rc == RT_OK) rc = check_last_row("rt_render", a.tiling, a.height);
+    if (rc != RT_OK) return rc;
+    if (scene.dev.depth > (uint32_t)dev::kStackMax) {
         set_error("rt_render: BVH deeper than the traversal stack");
         return RT_ERR_UNSUPPORTED;
     }
-    dev::KParams P;
+    return RT_OK;
+}
+
+// Everything of KParams that does not depend on the kernel: scene, outputs, frame, camera, RNG, diagnostics
+int fill_render_params(dev::KParams& P, const DeviceScene& S, const rt_render_args& a) {
     std::memset(&P, 0, sizeof(P));
-    P.nodes = (const float4*)S.nodes;
-    P.nodes48 = (const float4*)S.nodes48;
-    P.refs = (const uint32_t*)S.refs;
-    P.prims = (const float4*)S.prims;
-    P.mats = (const float4*)S.mats;
-    P.imgs = (const int4*)S.imgs;
-    P.texels = (const uint8_t*)S.texels;
-    P.pos = a->pos;
-    P.radiance = (float4*)a->radiance;
-    P.accum = (float4*)a->accum;
-    P.state = (uint32_t*)a->state;
-    if (a->flags & RT_FLAG_STATE_SOA) {  // six planes of whole 8×8 tiles
-        const uint64_t plane = rt_soa_plane_words(a->width, T.local_rows);
+    fill_scene_tables(P, S);
+    P.bvh_ref_nodes = (const float4*)S.bvh_ref_nodes;  // (the BVH kernels' exactness, bvh_clear)
+    P.bvh_boxes = (const float4*)S.bvh_boxes;
+    P.bvh_ref_pairs = (const float4*)S.bvh_ref_pairs;
+    P.bvh_has_rects = S.has_rects ? 1u : 0u;
+    P.pos = a.pos;
+    P.radiance = (float4*)a.radiance;
+    P.accum = (float4*)a.accum;
+    P.state = (uint32_t*)a.state;
+    P.state_stride = 1u;
+    if (a.flags & RT_FLAG_STATE_SOA) {  // six planes of whole 8×8 tiles
+        const uint64_t plane = rt_soa_plane_words(a.width, a.tiling.local_rows);
         if (plane > 0xffffffffull) {
             set_error("rt_render: RT_FLAG_STATE_SOA needs < 2^32 pixels per rank");
             return RT_ERR_INVALID_ARGUMENT;
         }
         P.state_stride = (uint32_t)plane;
-    } else {
-        P.state_stride = 1u;
     }
-    P.counters = (unsigned long long*)a->counters;
-    P.num_nodes = S.num_nodes;
-    P.num_prims = S.num_prims;
-    P.num_mats = S.num_mats;
-    P.num_imgs = S.num_imgs;
-    P.width = a->width;
-    P.height = a->height;
-    P.spp = a->samples_per_pixel;
-    P.max_depth = a->max_depth;
-    P.flags = a->flags;
-    P.band_rows = T.band_rows;
-    P.num_ranks = T.num_ranks;
-    P.rank = T.rank;
-    P.local_rows = T.local_rows;
-    P.tiles_x = 0;  // set below for the chosen workgroup shape
-    const bool faithful = (a->flags & RT_FLAG_FAITHFUL_GRID) != 0;
-    P.grid_w = faithful ? (a->width / 16) * 16 : a->width;
-    P.grid_h = faithful ? (a->height / 16) * 16 : a->height;
-    P.rius_rtl = (a->flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
+    P.counters = (unsigned long long*)a.counters;
+    P.spp = a.samples_per_pixel;
+    P.max_depth = a.max_depth;
+    P.flags = a.flags;
+    fill_frame(P, a.width, a.height, a.tiling, (a.flags & RT_FLAG_FAITHFUL_GRID) != 0);
+    fill_camera(P, a.inputs, a.width, a.height);
+    P.rius_rtl = (a.flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
     P.regen_threshold = (uint32_t)g_regen_threshold;
     P.regen_live_frac = (uint32_t)g_regen_live_frac;
     P.leaf_break = (uint32_t)g_leaf_break;
-    P.rng_key_lo = (uint32_t)a->rng_seed;
-    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
-    P.rng_frame = a->rng_frame;
+    P.prefetch_stop = (uint32_t)g_prefetch_stop;
+    P.rng_key_lo = (uint32_t)a.rng_seed;
+    P.rng_key_hi = (uint32_t)(a.rng_seed >> 32);
+    P.rng_frame = a.rng_frame;
     P.wave_trace = g_wave_trace;
     P.wave_trace_words = g_wave_trace_words;
     P.tile_order = g_tile_order;
@@ -4945,276 +4808,304 @@ int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) 
     P.ray_dump_count = g_ray_dump_count;
     P.ray_dump_cap = g_ray_dump_cap;
     P.ray_dump_depth = g_ray_dump_depth;
-    fill_camera(P, a->inputs, a->width, a->height);
+    return RT_OK;
+}
 
-    const bool count_tests = a->counters && (a->flags & RT_FLAG_COUNT_TESTS);
-    int variant = g_variant;
-    // auto: the fastest measured kernel per workload shape (profiles/r01d_*, r01e_*): the persistent v4 when a
-    // pixel has few paths (config 5: 1 spp, 0.51-0.54 vs 0.80 ms), otherwise v3 with the adaptive
-    // longest-first tile order and compact parking: 13 words of parked state + a depth + 2 stack fit config
-    // 2's wave in 5 KB of LDS, 8 waves per SIMD (config 2: 17.05 vs 17.8 ms with 15-word parking; config 3,
-    // depth 16: 365 vs 408 ms for v4).  Compact parking falls back to 15 words where its packed counters
-    // would overflow.
-    std::shared_ptr<AutoChoice> trial;  // this frame is timed for the automatic choice: events ev[trial_slot..+1]
-    int trial_slot = 0;
-    const bool automatic = variant < 0 || variant >= kNumVariants;
-    // small scenes: the flat kernel takes v3's place (in the trial below 64 spp as well).  (Until round 5 also scenes of
-    // up to kFlatMaxPrims primitives whose rectangles touch others, where only the flat kernels were exact; the BVH
-    // kernels now replay the reference traversal where it could differ, bvh_clear, and are faster beyond 16.)
-    const bool flat_ok = S.prims_flat && S.num_prims <= (uint32_t)g_flat_max;
-    const int tile_kernel = flat_ok ? kVarFlat : kVarV3Compact;
-    const int persistent_kernel = flat_ok ? kVarFlatPersistent : kVarV4;
-    if (automatic) {
-        variant = a->samples_per_pixel < 32 ? persistent_kernel : tile_kernel;
-        if (a->samples_per_pixel > 0 && a->samples_per_pixel < kAutoSpp && a->max_depth > 0) {
-            int device = 0;
-            (void)hipGetDevice(&device);
-            const AutoKey key{device, stream, scene, a->width, T.local_rows, a->samples_per_pixel, a->max_depth,
-                              philox ? 1u : 0u, flat_ok ? 1u : 0u};
-            std::lock_guard<std::mutex> lock(g_auto_mu);
-            auto it = g_auto.find(key);
-            if (it == g_auto.end()) {
-                if (g_auto.size() >= 64) g_auto.clear();
-                it = g_auto.emplace(key, std::make_shared<AutoChoice>()).first;
-            }
-            const std::shared_ptr<AutoChoice> held = it->second;
-            AutoChoice& ac = *held;
-            if (ac.chosen >= 0) {
-                variant = ac.chosen;
-            } else if (ac.stage < 3) {
-                variant = ac.stage < 2 ? tile_kernel : persistent_kernel;
-                if (ac.stage >= 1) {
-                    trial_slot = ac.stage == 1 ? 0 : 2;
-                    if ((ac.ev[trial_slot] || hipEventCreate(&ac.ev[trial_slot]) == hipSuccess) &&
-                        (ac.ev[trial_slot + 1] || hipEventCreate(&ac.ev[trial_slot + 1]) == hipSuccess))
-                        trial = held;
-                }
-                ac.stage++;
-            } else if (ac.ev[1] && ac.ev[3] && hipEventQuery(ac.ev[1]) == hipSuccess &&
-                       hipEventQuery(ac.ev[3]) == hipSuccess) {
-                float t3 = -1.0f, t4 = -1.0f;
-                (void)hipEventElapsedTime(&t3, ac.ev[0], ac.ev[1]);
-                (void)hipEventElapsedTime(&t4, ac.ev[2], ac.ev[3]);
-                ac.chosen = (t3 >= 0.0f && t4 >= 0.0f && t4 < t3) ? persistent_kernel : tile_kernel;
-                variant = ac.chosen;
-            } else if (!ac.ev[1] || !ac.ev[3]) {
-                ac.chosen = variant;  // no events: keep the static rule
-            }
-            (void)hipGetLastError();  // (hipEventQuery reports hipErrorNotReady while pending)
-        }
+// A frame of the automatic choice's trial: the render kernel runs between ev[slot] and ev[slot + 1] of `timed`
+struct Trial {
+    std::shared_ptr<AutoChoice> timed;
+    int slot = 0;
+};
+
+// The automatic choice below kAutoSpp (AutoChoice): the trial's next kernel, or the pair's faster one once both are
+// timed; `variant` (the static rule's) until then
+int trial_variant(int variant, const AutoKey& key, Trial* trial) {
+    const int tile_kernel = tile_kernel_of(key.flat != 0u), persistent_kernel = persistent_kernel_of(key.flat != 0u);
+    std::lock_guard<std::mutex> lock(g_auto_mu);
+    auto it = g_auto.find(key);
+    if (it == g_auto.end()) {
+        if (g_auto.size() >= 64) g_auto.clear();
+        it = g_auto.emplace(key, std::make_shared<AutoChoice>()).first;
     }
-    const bool packable =
-        a->samples_per_pixel < 8192u && a->max_depth < 64u && (uint64_t)a->samples_per_pixel * a->max_depth < 8192u;
-    if (variant == kVarFlat && !S.prims_flat) variant = kVarV3Compact;  // (a scene beyond kFlatMaxPrims)
-    // the persistent flat kernel stages the flat tables in LDS: a scene whose materials overflow kFlatTabLdsMax runs v4
-    const size_t flat_tab_bytes = ((size_t)4 * S.num_prims + (size_t)3 * S.num_mats + S.num_imgs) * 16u;
-    if (variant == kVarFlatPersistent && (!S.prims_flat || flat_tab_bytes > kFlatTabLdsMax)) variant = kVarV4;
-    if (kVariants[variant].compact && !packable) variant = kVarV3;  // packed counters would overflow
-    if ((kVariants[variant].kernel == 4 || kVariants[variant].kernel == 6) && (a->samples_per_pixel == 0 || a->max_depth == 0))
-        variant = kVariants[variant].kernel == 6 ? kVarFlat  // the persistent kernels assume every pixel traces a ray
-                                                 : (packable ? kVarV3Compact : kVarV3);
-    if (philox && kVariants[variant].stack != dev::STACK_LDS16 && kVariants[variant].stack != dev::STACK_NONE)
-        variant = packable ? kVarV3Compact : kVarV3;  // the v1/v2 kernels have no Philox build
-    // Scenes whose references need 32 bits (S.wide_refs: >= 32767 nodes or >= 8192 primitives) run the WIDE builds
-    // of the compact v3 and of v4; the 15-word v3 has none: v2 / v1 there (no Philox build either).
-    bool wide = false;
-    if (kVariants[variant].stack == dev::STACK_LDS16 && S.wide_refs) {
-        if (variant == kVarV3) {
-            if (philox) {
-                set_error("rt_render: RT_FLAG_RNG_PHILOX on a scene with 32-bit references needs spp < 8192, "
-                          "max_depth < 64 and spp * max_depth < 8192");
-                return RT_ERR_UNSUPPORTED;
-            }
-            variant = S.depth <= 25u ? kVarV2 : kVarV1;  // 32-bit LDS stacks, or scratch if deep
-        } else {
-            wide = true;
+    const std::shared_ptr<AutoChoice> held = it->second;
+    AutoChoice& ac = *held;
+    if (ac.chosen >= 0) {
+        variant = ac.chosen;
+    } else if (ac.stage < 3) {
+        variant = ac.stage < 2 ? tile_kernel : persistent_kernel;
+        if (ac.stage >= 1) {
+            trial->slot = ac.stage == 1 ? 0 : 2;
+            if ((ac.ev[trial->slot] || hipEventCreate(&ac.ev[trial->slot]) == hipSuccess) &&
+                (ac.ev[trial->slot + 1] || hipEventCreate(&ac.ev[trial->slot + 1]) == hipSuccess))
+                trial->timed = held;
         }
+        ac.stage++;
+    } else if (ac.ev[1] && ac.ev[3] && hipEventQuery(ac.ev[1]) == hipSuccess && hipEventQuery(ac.ev[3]) == hipSuccess) {
+        float t3 = -1.0f, t4 = -1.0f;
+        (void)hipEventElapsedTime(&t3, ac.ev[0], ac.ev[1]);
+        (void)hipEventElapsedTime(&t4, ac.ev[2], ac.ev[3]);
+        ac.chosen = (t3 >= 0.0f && t4 >= 0.0f && t4 < t3) ? persistent_kernel : tile_kernel;
+        variant = ac.chosen;
+    } else if (!ac.ev[1] || !ac.ev[3]) {
+        ac.chosen = variant;  // no events: keep the static rule
     }
+    (void)hipGetLastError();  // (hipEventQuery reports hipErrorNotReady while pending)
+    return variant;
+}
+
+// The variant this frame asks for: rt_set_variant's, else the automatic choice
+int requested_variant(const rt_scene* scene, const rt_render_args& a, rt_stream stream, Trial* trial) {
+    if (g_variant >= 0 && g_variant < kNumVariants) return g_variant;
+    const DeviceScene& S = scene->dev;
+    const int variant = static_variant(a.samples_per_pixel, S.prims_flat != nullptr, S.num_prims, (uint32_t)g_flat_max);
+    if (a.samples_per_pixel == 0 || a.samples_per_pixel >= kAutoSpp || a.max_depth == 0) return variant;
+    int device = 0;
+    (void)hipGetDevice(&device);
+    const bool flat = variant == kVarFlat || variant == kVarFlatPersistent;
+    return trial_variant(variant, AutoKey{device, stream, scene, a.width, a.tiling.local_rows, a.samples_per_pixel,
+                                          a.max_depth, (a.flags & RT_FLAG_RNG_PHILOX) ? 1u : 0u, flat ? 1u : 0u}, trial);
+}
+
+// The workgroup and its LDS (no device call).  v3/v4: per wave, the parked path state + a 16-bit stack of depth + 2
+// entries: two sentinel pads, and a visit at level L (root = 1) holds at most L - 1 deferred children, so its
+// unconditional write of the far child lands at index 2 + (L - 1) <= depth + 1 (the 128-B saving keeps config 2's
+// wave inside 10 × 512 B of LDS)
+struct LaunchShape {
+    uint32_t block;       // threads per workgroup
+    uint32_t wave_words;  // KParams::lds_wave_words
+    size_t lds_bytes;
+    bool group;           // the persistent flat kernel's GROUP build: 16-wave workgroups (one per CU) whose share
+                          // counter follows the tables
+    int group_per_cu;     // GROUP: the workgroups per CU the grid is sized for (kFlatPersistentWaves waves per SIMD,
+                          // e.g. 1 of 16 waves)
+};
+LaunchShape launch_shape(const int variant, const bool wide, const uint32_t bvh_depth, const size_t flat_tab_bytes) {
     const Variant& V = kVariants[variant];
     const bool persistent = V.kernel == 4 || V.kernel == 6;
-    // near-first traversal holds at most one deferred child per level below the root
-    if (V.stack == dev::STACK_LDS && S.depth > (uint32_t)V.lds_depth + 1) {
-        set_error("rt_render: BVH too deep for the LDS stack of kernel variant " + std::to_string(variant));
-        return RT_ERR_UNSUPPORTED;
-    }
-    // v3/v4: per wave, the parked path state + a 16-bit stack of depth + 2 entries: two sentinel pads, and
-    // a visit at level L (root = 1) holds at most L - 1 deferred children, so its unconditional write of
-    // the far child lands at index 2 + (L - 1) <= depth + 1 (the 128-B saving keeps config 2's wave
-    // inside 10 × 512 B of LDS)
-    const int group_mode = V.kernel == 6 ? g_persistent_group : 0;
     const size_t wave_bytes = V.stack == dev::STACK_LDS16
                                   ? (size_t)(persistent ? dev::PK_WORDS4 : dev::park_words(V.compact)) * 64 * 4 +
-                                        (size_t)(S.depth + 2) * 64 * (wide ? 4 : 2) + (size_t)g_lds_pad
+                                        (size_t)(bvh_depth + 2) * 64 * (wide ? 4 : 2) + (size_t)g_lds_pad
                                   : 0;
-    P.lds_wave_words = (uint32_t)(wave_bytes / 4);
-    // the persistent flat kernel's GROUP build: 16-wave workgroups (one per CU) whose share counter follows the tables
-    const bool group = V.kernel == 6 && g_persistent_group != 0;
-    const uint32_t block = group ? (uint32_t)g_group_waves * 64u : (uint32_t)V.block;
-    // GROUP: the workgroups per CU the grid is sized for (kFlatPersistentWaves waves per SIMD, e.g. 1 of 16 waves)
-    const int group_per_cu = std::max(1, kFlatPersistentWaves * 4 / std::max(1, g_group_waves));
-    size_t lds_bytes = (V.stack == dev::STACK_LDS ? (size_t)V.lds_depth * V.block * 4 : 0) + wave_bytes +
-                       (V.kernel == 6 ? flat_tab_bytes + (group ? 4u * (2u + dev::kGqWords) : 0u) : 0);  // (GROUP)
-    if (lds_bytes > kLdsLimit) {
-        set_error("rt_render: BVH too deep for the LDS stack of kernel variant " + std::to_string(variant));
-        return RT_ERR_UNSUPPORTED;
+    LaunchShape L;
+    L.group = V.kernel == 6 && g_persistent_group != 0;
+    L.block = L.group ? (uint32_t)g_group_waves * 64u : (uint32_t)V.block;
+    L.wave_words = (uint32_t)(wave_bytes / 4);
+    L.group_per_cu = std::max(1, kFlatPersistentWaves * 4 / std::max(1, g_group_waves));
+    L.lds_bytes = (V.stack == dev::STACK_LDS ? (size_t)V.lds_depth * V.block * 4 : 0) + wave_bytes +
+                  (V.kernel == 6 ? flat_tab_bytes + (L.group ? 4u * (2u + dev::kGqWords) : 0u) : 0);  // (GROUP)
+    return L;
+}
+
+// GROUP shares in golden-ratio order (RT_TUNE_GROUP_ORDER 1): share g holds tiles (j · A) mod S for j in
+// [g·K, g·K + K), A ≈ 0.618 S coprime with S — every share (and every XCD's) a spread sample of the frame, and
+// the tiles the groups render at one moment scattered over it, not one band or one comb of tile columns
+void fill_group_order(dev::KParams& P, const bool group, const uint32_t grid) {
+    P.group_perm_a = P.group_perm_b = P.group_perm_k = 0u;
+    const uint64_t S = P.group_tiles;
+    if (!group || g_group_order != 1 || S <= 1u) return;
+    const uint64_t K = (S + grid - 1u) / grid;
+    uint64_t A = (uint64_t)((double)S * 0.6180339887498949) | 1u;
+    while (std::gcd(A, S) != 1u) A++;
+    if ((uint64_t)(grid - 1u) * (S - 1u) + (K - 1u) * (S - 1u) < (1ull << 32)) {
+        P.group_perm_a = (uint32_t)A;
+        P.group_perm_b = (uint32_t)(K * A % S);
+        P.group_perm_k = (uint32_t)K;
     }
-    KernelFn fn = pick(variant, count_tests, S.has_textures, philox, wide, g_wave_trace != nullptr);
-    P.bvh_ref_nodes = (const float4*)S.bvh_ref_nodes;  // (the BVH kernels' exactness, bvh_clear)
-    P.bvh_boxes = (const float4*)S.bvh_boxes;
-    P.bvh_ref_pairs = (const float4*)S.bvh_ref_pairs;
-    P.bvh_has_rects = S.has_rects ? 1u : 0u;
-    P.prefetch_stop = (uint32_t)g_prefetch_stop;
-    if (V.kernel == 5 || V.kernel == 6) {  // the flat kernels' tables: primitives in the reference's test order, its BVH
-        P.prims = (const float4*)S.prims_flat;
-        P.ref_nodes = (const float4*)S.ref_nodes;
-        P.flat_ref_pairs = (const float4*)S.flat_ref_pairs;
-        P.flat_boxes = (const float4*)S.flat_boxes;
-        P.flat_runs[0] = S.flat_runs[0];
-        P.flat_runs[1] = S.flat_runs[1];
+}
+
+// A persistent launch: its queue slot, the grid that fills the device, the queue's and the GROUP shares' terms
+int setup_persistent(dev::KParams& P, const int kernel, const KernelFn fn, const uint32_t tiles, hipStream_t s,
+                     LaunchShape& L, uint32_t* grid) {
+    int device = 0, cus = 0, per_cu = 0;
+    int rc = hip_check(hipGetDevice(&device), "rt_render: hipGetDevice");
+    if (rc == RT_OK) rc = acquire_queue(device, (uint32_t)g_queue_stride, &P.work_counter, &cus);
+    if (rc == RT_OK)
+        rc = hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, L.block, L.lds_bytes),
+                       "rt_render: occupancy query");
+    if (rc != RT_OK) return rc;
+    if (L.group && per_cu > L.group_per_cu) {
+        // more groups would fit a CU by registers than the grid is sized for: claim enough of the CU's LDS that
+        // the grid cannot put more on one CU and leave another short
+        L.lds_bytes = std::max(L.lds_bytes, kLdsLimit / (size_t)(L.group_per_cu + 1) + 1024u);
+        rc = hip_check(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bytes),
+                       "rt_render: LDS size attribute");
+        if (rc != RT_OK) return rc;
     }
+    P.work_total = tiles * 64u;
+    P.pixel_cost = g_pixel_cost_bytes >= (uint64_t)P.work_total ? g_pixel_cost : nullptr;
+    P.work_chunk = (uint32_t)g_queue_chunk;
+    P.queue_prefetch = (uint32_t)g_queue_prefetch;
+    P.queue_min = (uint32_t)g_queue_min;
+    P.queue_stride = (uint32_t)g_queue_stride / 4u;
+    // GROUP: the groups' static shares cover the first tiles, the per-wave queue the last g_group_tail permille
+    const uint32_t tail_tiles =
+        L.group && g_persistent_group == 1 ? (uint32_t)(((uint64_t)tiles * (uint32_t)g_group_tail + 999u) / 1000u) : tiles;
+    P.group_chunk = (uint32_t)g_group_chunk;
+    P.linger_ticks = L.group ? (uint32_t)g_group_linger_us * 100u : 0u;
+    P.group_tiles = tiles - tail_tiles;
+    P.queue_base = P.group_tiles * 64u;
+    P.work_per_counter = (tail_tiles + dev::kQueueCounters - 1u) / dev::kQueueCounters * 64u;
+    // the persistent flat kernel runs 4 waves per SIMD even where its registers allow 5-6: C5 0.294 vs 0.307 ms
+    // (XORWOW), 0.300 vs 0.314 (Philox), 3 rounds on one box (profiles/r04f_ab_pflat_waves.txt)
+    if (kernel == 6)
+        per_cu = std::min(per_cu, L.group ? L.group_per_cu : std::max(1, kFlatPersistentWaves * 4 * 64 / (int)L.block));
+    if (g_persistent_waves > 0) per_cu = std::max(1, g_persistent_waves * 4 * 64 / (int)L.block);
+    const uint64_t resident = (uint64_t)(per_cu > 0 ? per_cu : 1) * (uint64_t)(cus > 0 ? cus : 1);
+    *grid = tiles;
+    if (L.group) *grid = (tiles + L.block / 64u - 1u) / (L.block / 64u);  // (no more waves than tiles, as one-wave grids)
+    *grid = (uint32_t)(resident < *grid ? resident : *grid);
+    fill_group_order(P, L.group, *grid);
+    P.queue_guide = g_queue_guide > 0 ? std::max(1u, *grid / dev::kQueueCounters) * (uint32_t)g_queue_guide : 0u;
+    // (no reset here: the slot is zero, the previous launch that used it left it so, queue_release — unless
+    // RT_TUNE_QUEUE_RESET asks for the round-4 host memset)
+    P.queue_host_reset = g_queue_host_reset ? 1u : 0u;
+    if (!g_queue_host_reset) return RT_OK;
+    return hip_check(hipMemsetAsync(P.work_counter, 0, (size_t)dev::kQueueSlotWords * P.queue_stride * 4u, s),
+                     "rt_render: queue reset");
+}
+
+// v3 and the tile flat kernel: this tile grid's cost table, and the order planned from the last frame's costs
+int bind_tile_plan(dev::KParams& P, const int kernel, hipStream_t s, std::shared_ptr<TilePlan>* plan) {
+    if ((kernel != 3 && kernel != 5) || !g_adaptive_order || g_tile_order) return RT_OK;
+    int device = 0;
+    int rc = hip_check(hipGetDevice(&device), "rt_render: hipGetDevice");
+    if (rc == RT_OK) rc = acquire_plan(PlanKey{device, (void*)s, P.tiles_x, P.num_tiles, kernel}, s, plan);
+    if (rc != RT_OK) return rc;
+    P.tile_cost = (*plan)->cost;
+    P.tile_order = (*plan)->valid.load() ? (*plan)->order : nullptr;
+    return RT_OK;
+}
+
+// v3 on a 16-bit-reference scene: the tiles' entry records, refilled when what they were computed from changed.
+// *lock holds the table (EntryTable::mu) until the render launch that reads it is enqueued.
+int bind_tile_entries(dev::KParams& P, const int kernel, const DeviceScene& S, hipStream_t s,
+                      std::shared_ptr<EntryTable>* entries, std::unique_lock<std::mutex>* lock) {
+    if (kernel != 3 || S.wide_refs || !g_tile_entries || S.num_nodes == 0 || !S.nodes || P.band_rows % 8u != 0 ||
+        P.spp == 0 || P.max_depth == 0)
+        return RT_OK;
+    int device = 0;
+    int rc = hip_check(hipGetDevice(&device), "rt_render: hipGetDevice");
+    if (rc == RT_OK) rc = acquire_entry_table(device, s, P.tiles_x, P.num_tiles, entries);
+    if (rc != RT_OK) return rc;
+    EntryTable& E = **entries;
+    *lock = std::unique_lock<std::mutex>(E.mu);
+    const TileFrame F = tile_frame_of(P, S.wide_refs, S.depth);
+    if (!E.filled || E.scene_uid != S.uid || std::memcmp(&E.frame, &F, sizeof(F)) != 0) {
+        (void)hipGetLastError();
+        E.filled = false;
+        hipLaunchKernelGGL(dev::tile_entries_kernel, dim3((P.num_tiles + 63u) / 64u), dim3(64), 0, s, (const float*)S.nodes,
+                           (const float*)S.prims, F, E.rec, P.num_tiles);
+        rc = hip_check(hipGetLastError(), "rt_render: tile entry kernel launch", RT_ERR_LAUNCH);
+        if (rc != RT_OK) return rc;
+        E.filled = true;
+        E.scene_uid = S.uid;
+        E.frame = F;
+    }
+    P.tile_entries = (const uint4*)E.rec;
+    P.camera_resolve = g_camera_resolve == 1 ? kCameraResolveCap : (uint32_t)g_camera_resolve;
+    P.path_end_step = (uint32_t)g_path_end_step;
+    return RT_OK;
+}
+
+// What of KParams follows from the kernel: its LDS per wave, the flat kernels' tables, the tile grid
+void fill_kernel_params(dev::KParams& P, const Variant& V, const LaunchShape& L, const DeviceScene& S) {
+    P.lds_wave_words = L.wave_words;
+    if (V.kernel == 5 || V.kernel == 6) fill_flat_tables(P, S);
     const int rius_trips = V.kernel == 6 ? g_rius_trips_persistent : g_rius_trips;  // (the flat kernels')
     P.rius_cap = rius_trips > 0 ? (uint32_t)rius_trips : 0xffffffffu;
     const uint32_t tile = V.block == 64 ? 8u : 16u;  // v2/v3/v4: one 8×8 tile per wave
-    P.tiles_x = (a->width + tile - 1) / tile;
-    const uint32_t tiles = P.tiles_x * ((T.local_rows + tile - 1) / tile);
+    P.tiles_x = (P.width + tile - 1) / tile;
+    P.num_tiles = P.tiles_x * ((P.local_rows + tile - 1) / tile);
+}
+
+// rt_set_timing: the frame between two events on its stream, rt_last_kernel_ms
+void timing_begin(hipEvent_t ev[2], hipStream_t s) {
+    if (!g_timing) return;
+    (void)hipEventCreate(&ev[0]);
+    (void)hipEventCreate(&ev[1]);
+    (void)hipEventRecord(ev[0], s);
+}
+void timing_end(hipEvent_t ev[2], hipStream_t s, const int rc) {
+    if (!g_timing) return;
+    (void)hipEventRecord(ev[1], s);
+    g_last_ms = -1.0f;
+    if (rc == RT_OK && hipEventSynchronize(ev[1]) == hipSuccess) (void)hipEventElapsedTime(&g_last_ms, ev[0], ev[1]);
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+}
+
+}  // namespace
+
+int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) {
+    if (!scene || !a) { set_error("rt_render: NULL scene or args"); return RT_ERR_INVALID_ARGUMENT; }
+    if (a->tiling.local_rows == 0 || a->width == 0 || a->height == 0) return RT_OK;  // nothing to render
+    int rc = check_render_args(*scene, *a);
+    if (rc != RT_OK) return rc;
+    const DeviceScene& S = scene->dev;
+    dev::KParams P;
+    rc = fill_render_params(P, S, *a);
+    if (rc != RT_OK) return rc;
+
+    // which kernel: the request, then what this scene and frame make of it
+    const bool philox = (a->flags & RT_FLAG_RNG_PHILOX) != 0;
+    const size_t flat_tab_bytes = ((size_t)4 * S.num_prims + (size_t)3 * S.num_mats + S.num_imgs) * 16u;
+    Trial trial;  // set when this frame is timed for the automatic choice
+    const int requested = requested_variant(scene, *a, stream, &trial);
+    const VariantChoice choice = resolve_variant(
+        requested, VariantFacts{P.spp, P.max_depth, philox, S.prims_flat != nullptr, flat_tab_bytes, S.wide_refs, S.depth});
+    if (choice.status != RT_OK) {
+        set_error(choice.error);
+        return choice.status;
+    }
+    const int variant = choice.variant;
+    const Variant& V = kVariants[variant];
+    const bool persistent = V.kernel == 4 || V.kernel == 6;
+    LaunchShape L = launch_shape(variant, choice.wide, S.depth, flat_tab_bytes);
+    if (L.lds_bytes > kLdsLimit) {
+        set_error("rt_render: BVH too deep for the LDS stack of kernel variant " + std::to_string(variant));
+        return RT_ERR_UNSUPPORTED;
+    }
+    const bool count_tests = a->counters && (a->flags & RT_FLAG_COUNT_TESTS);
+    KernelFn fn = pick(variant, count_tests, S.has_textures, philox, choice.wide, g_wave_trace != nullptr);
+    fill_kernel_params(P, V, L, S);
+
+    // what the launch reads: queue slot, tile plan, tile entry records (held until the launch is enqueued)
     hipStream_t s = (hipStream_t)stream;
-    uint32_t grid = tiles;
-    if (persistent) {
-        int device = 0, cus = 0, per_cu = 0;
-        int rc = hip_check(hipGetDevice(&device), "rt_render: hipGetDevice");
-        if (rc == RT_OK) rc = acquire_queue(device, (uint32_t)g_queue_stride, &P.work_counter, &cus);
-        if (rc == RT_OK)
-            rc = hip_check(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)fn, block, lds_bytes),
-                           "rt_render: occupancy query");
-        if (rc != RT_OK) return rc;
-        if (group && per_cu > group_per_cu) {
-            // more groups would fit a CU by registers than the grid is sized for: claim enough of the CU's LDS that
-            // the grid cannot put more on one CU and leave another short
-            lds_bytes = std::max(lds_bytes, kLdsLimit / (size_t)(group_per_cu + 1) + 1024u);
-            rc = hip_check(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes),
-                           "rt_render: LDS size attribute");
-            if (rc != RT_OK) return rc;
-        }
-        P.work_total = tiles * 64u;
-        P.pixel_cost = g_pixel_cost_bytes >= (uint64_t)P.work_total ? g_pixel_cost : nullptr;
-        P.work_chunk = (uint32_t)g_queue_chunk;
-        P.queue_prefetch = (uint32_t)g_queue_prefetch;
-        P.queue_min = (uint32_t)g_queue_min;
-        P.queue_stride = (uint32_t)g_queue_stride / 4u;
-        // GROUP: the groups' static shares cover the first tiles, the per-wave queue the last g_group_tail permille
-        const uint32_t tail_tiles =
-            group && group_mode == 1 ? (uint32_t)(((uint64_t)tiles * (uint32_t)g_group_tail + 999u) / 1000u) : tiles;
-        P.group_chunk = (uint32_t)g_group_chunk;
-        P.linger_ticks = group ? (uint32_t)g_group_linger_us * 100u : 0u;
-        P.group_tiles = tiles - tail_tiles;
-        P.queue_base = P.group_tiles * 64u;
-        P.work_per_counter = (tail_tiles + dev::kQueueCounters - 1u) / dev::kQueueCounters * 64u;
-        // the persistent flat kernel runs 4 waves per SIMD even where its registers allow 5-6: C5 0.294 vs 0.307 ms
-        // (XORWOW), 0.300 vs 0.314 (Philox), 3 rounds on one box (profiles/r04f_ab_pflat_waves.txt)
-        if (V.kernel == 6) per_cu = std::min(per_cu, group ? group_per_cu : std::max(1, kFlatPersistentWaves * 4 * 64 / (int)block));
-        if (g_persistent_waves > 0) per_cu = std::max(1, g_persistent_waves * 4 * 64 / (int)block);
-        const uint64_t resident = (uint64_t)(per_cu > 0 ? per_cu : 1) * (uint64_t)(cus > 0 ? cus : 1);
-        if (group) grid = (tiles + block / 64u - 1u) / (block / 64u);  // (no more waves than tiles, as one-wave grids)
-        grid = (uint32_t)(resident < grid ? resident : grid);
-        // GROUP shares in golden-ratio order (RT_TUNE_GROUP_ORDER 1): share g holds tiles (j · A) mod S for j in
-        // [g·K, g·K + K), A ≈ 0.618 S coprime with S — every share (and every XCD's) a spread sample of the frame, and
-        // the tiles the groups render at one moment scattered over it, not one band or one comb of tile columns
-        P.group_perm_a = P.group_perm_b = P.group_perm_k = 0u;
-        const uint64_t S = P.group_tiles;
-        if (group && g_group_order == 1 && S > 1u) {
-            const uint64_t K = (S + grid - 1u) / grid;
-            uint64_t A = (uint64_t)((double)S * 0.6180339887498949) | 1u;
-            while (std::gcd(A, S) != 1u) A++;
-            if ((uint64_t)(grid - 1u) * (S - 1u) + (K - 1u) * (S - 1u) < (1ull << 32)) {
-                P.group_perm_a = (uint32_t)A;
-                P.group_perm_b = (uint32_t)(K * A % S);
-                P.group_perm_k = (uint32_t)K;
-            }
-        }
-        P.queue_guide = g_queue_guide > 0 ? std::max(1u, grid / dev::kQueueCounters) * (uint32_t)g_queue_guide : 0u;
-        // (no reset here: the slot is zero, the previous launch that used it left it so, queue_release — unless
-        // RT_TUNE_QUEUE_RESET asks for the round-4 host memset)
-        P.queue_host_reset = g_queue_host_reset ? 1u : 0u;
-        if (g_queue_host_reset) {
-            int rc2 = hip_check(hipMemsetAsync(P.work_counter, 0, (size_t)dev::kQueueSlotWords * P.queue_stride * 4u, s),
-                                "rt_render: queue reset");
-            if (rc2 != RT_OK) return rc2;
-        }
-    }
-    P.num_tiles = tiles;
+    uint32_t grid = P.num_tiles;
+    if (persistent) rc = setup_persistent(P, V.kernel, fn, P.num_tiles, s, L, &grid);
+    if (rc != RT_OK) return rc;
     std::shared_ptr<TilePlan> plan;
-    if ((V.kernel == 3 || V.kernel == 5) && g_adaptive_order && !g_tile_order) {
-        int device = 0;
-        int rc = hip_check(hipGetDevice(&device), "rt_render: hipGetDevice");
-        if (rc == RT_OK) rc = acquire_plan(PlanKey{device, (void*)s, P.tiles_x, tiles, V.kernel}, s, &plan);
-        if (rc != RT_OK) return rc;
-        P.tile_cost = plan->cost;
-        P.tile_order = plan->valid.load() ? plan->order : nullptr;
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_timing) {
-        (void)hipEventCreate(&e0);
-        (void)hipEventCreate(&e1);
-        (void)hipEventRecord(e0, s);
-    }
+    rc = bind_tile_plan(P, V.kernel, s, &plan);
+    if (rc != RT_OK) return rc;
+    hipEvent_t timing[2] = {nullptr, nullptr};
+    timing_begin(timing, s);
     g_last_variant = variant;
-    // v3 on a 16-bit-reference scene: the tiles' entry records, refilled when what they were computed from changed
     std::shared_ptr<EntryTable> entries;
     std::unique_lock<std::mutex> entries_lock;
-    if (V.kernel == 3 && !wide && !S.wide_refs && g_tile_entries && S.num_nodes > 0 && S.nodes && T.band_rows % 8u == 0 &&
-        a->samples_per_pixel > 0 && a->max_depth > 0) {
-        int device = 0;
-        int rc = hip_check(hipGetDevice(&device), "rt_render: hipGetDevice");
-        if (rc == RT_OK) rc = acquire_entry_table(device, s, P.tiles_x, tiles, &entries);
-        if (rc != RT_OK) return rc;
-        entries_lock = std::unique_lock<std::mutex>(entries->mu);
-        const TileFrame F = tile_frame_of(P, S.wide_refs, S.depth);
-        if (!entries->filled || entries->scene_uid != S.uid || std::memcmp(&entries->frame, &F, sizeof(F)) != 0) {
-            (void)hipGetLastError();
-            entries->filled = false;
-            hipLaunchKernelGGL(dev::tile_entries_kernel, dim3((tiles + 63u) / 64u), dim3(64), 0, s, (const float*)S.nodes,
-                               (const float*)S.prims, F, entries->rec, tiles);
-            rc = hip_check(hipGetLastError(), "rt_render: tile entry kernel launch", RT_ERR_LAUNCH);
-            if (rc != RT_OK) return rc;
-            entries->filled = true;
-            entries->scene_uid = S.uid;
-            entries->frame = F;
-        }
-        P.tile_entries = (const uint4*)entries->rec;
-        P.camera_resolve = g_camera_resolve == 1 ? kCameraResolveCap : (uint32_t)g_camera_resolve;
-        P.path_end_step = (uint32_t)g_path_end_step;
-    }
-    if (trial) (void)hipEventRecord(trial->ev[trial_slot], s);
+    rc = bind_tile_entries(P, V.kernel, S, s, &entries, &entries_lock);
+    if (rc != RT_OK) return rc;
+
+    if (trial.timed) (void)hipEventRecord(trial.timed->ev[trial.slot], s);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(fn, dim3(grid), dim3(block), lds_bytes, s, P);
-    int rc = hip_check(hipGetLastError(), "rt_render: kernel launch", RT_ERR_LAUNCH);
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(L.block), L.lds_bytes, s, P);
+    rc = hip_check(hipGetLastError(), "rt_render: kernel launch", RT_ERR_LAUNCH);
     if (entries_lock.owns_lock()) entries_lock.unlock();
     // A persistent launch that did not run leaves its queue slot as it found it, but the slot is re-zeroed anyway, so
     // that the launch reusing it kQueueSlots launches later never finds exhausted heads (the slot is
     // otherwise clean only because the grid's last wave zeroes it in queue_release)
     if (rc != RT_OK && persistent)
         (void)hipMemsetAsync(P.work_counter, 0, (size_t)dev::kQueueSlotWords * P.queue_stride * 4u, s);
-    if (trial) (void)hipEventRecord(trial->ev[trial_slot + 1], s);  // the render kernel alone (v4 has no plan step)
+    if (trial.timed) (void)hipEventRecord(trial.timed->ev[trial.slot + 1], s);  // the render kernel alone (v4 has no plan step)
     if (rc == RT_OK && plan) {  // the next launch on this stream dispatches this frame's costliest tiles first
         hipLaunchKernelGGL(dev::plan_order_kernel, dim3(1), dim3(1024), 0, s, (const uint32_t*)plan->cost, plan->order,
-                           tiles);
+                           P.num_tiles);
         rc = hip_check(hipGetLastError(), "rt_render: plan kernel launch", RT_ERR_LAUNCH);
         if (rc == RT_OK) plan->valid.store(true);
     }
-    if (g_timing) {
-        (void)hipEventRecord(e1, s);
-        if (rc == RT_OK && hipEventSynchronize(e1) == hipSuccess) {
-            float ms = -1.0f;
-            (void)hipEventElapsedTime(&ms, e0, e1);
-            g_last_ms = ms;
-        } else {
-            g_last_ms = -1.0f;
-        }
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-    }
+    timing_end(timing, s, rc);
     return rc;
 }
+
 
 uint64_t rt_soa_plane_words(uint32_t width, uint32_t local_rows) {
     return (((uint64_t)width + 7u) / 8u) * (((uint64_t)local_rows + 7u) / 8u) * 64u;
@@ -5226,10 +5117,7 @@ int render_init(void* d_state, uint32_t width, const rt_tiling* tiling, uint64_t
     if (!tiling) { set_error(std::string(who) + ": NULL tiling"); return RT_ERR_INVALID_ARGUMENT; }
     if ((size_t)width * tiling->local_rows == 0) return RT_OK;  // nothing to seed
     if (!d_state) { set_error(std::string(who) + ": NULL state"); return RT_ERR_INVALID_ARGUMENT; }
-    if (tiling->band_rows == 0 || tiling->num_ranks == 0 || tiling->rank >= tiling->num_ranks) {
-        set_error(std::string(who) + ": invalid tiling");
-        return RT_ERR_INVALID_ARGUMENT;
-    }
+    if (const int rc = check_tiling(who, *tiling); rc != RT_OK) return rc;
     const size_t n = (size_t)width * tiling->local_rows;
     if (soa) {
         const uint64_t plane = rt_soa_plane_words(width, tiling->local_rows);

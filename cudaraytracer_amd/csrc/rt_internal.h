@@ -41,7 +41,7 @@ namespace rt {
 
 constexpr int kLeafMax = 4;         // max primitives per leaf (2-bit count in the leaf reference)
 // Deepest BVH the compact v3 kernel holds at 8 waves per SIMD: 13 parked words × 256 B + (depth + 2) × 128 B of
-// 16-bit stack per wave must fit 160 KB / 32 waves = 5120 B (render.hip, rt_render's LDS sizing)
+// 16-bit stack per wave must fit 160 KB / 32 waves = 5120 B (render.hip, launch_shape)
 constexpr uint32_t kOccupancyDepth = 12;
 extern thread_local int g_leaf_max;  // rt_set_tuning(RT_TUNE_LEAF_MAX): 1..kLeafMax, read by the BVH build
 extern thread_local int g_sah_traversal_x10;  // rt_set_tuning(RT_TUNE_SAH_TRAVERSAL): SAH node cost × 10
@@ -117,6 +117,27 @@ struct FlatDesc {
 int flatten_reference_graph(const void* world, FlatDesc* out, std::string* err);
 
 void set_error(const std::string& msg);
+
+// rt_render's kernel choice (render.hip): arithmetic on a few facts of the scene and the frame, with no device call and
+// no global, so the stand-alone host driver can walk its cases (tests/native/host_sanitize.cpp).
+struct VariantFacts {
+    uint32_t spp, max_depth;
+    bool philox;            // RT_FLAG_RNG_PHILOX
+    bool prims_flat;        // the scene has the flat kernels' tables
+    size_t flat_tab_bytes;  // ... the bytes of them the persistent flat kernel stages in LDS
+    bool wide_refs;         // HostScene::wide_refs
+    uint32_t bvh_depth;     // HostScene::depth
+};
+struct VariantChoice {
+    int variant;        // index into rt_set_variant's table
+    bool wide;          // the 32-bit-reference build of it
+    int status;         // RT_OK, or RT_ERR_UNSUPPORTED with `error`
+    std::string error;
+};
+// The automatic choice by spp alone (below 64 spp rt_render times it against the other kernel of the pair)
+int static_variant(uint32_t spp, bool prims_flat, uint32_t num_prims, uint32_t flat_max);
+// The kernel that runs when `variant` (0..6) is asked for
+VariantChoice resolve_variant(int variant, const VariantFacts& f);
 
 // Do the byte ranges [a, a + na) and [b, b + nb) share a byte?  (A NULL or empty range shares none.)
 inline bool overlaps(const void* a, const uint64_t na, const void* b, const uint64_t nb) {

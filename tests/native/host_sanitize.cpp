@@ -349,7 +349,72 @@ static void node_reference_payload() {
     CHECK(rt::build_host_scene(&d, &hs, &err, false) == RT_ERR_INVALID_SCENE);
 }
 
+// rt_render's kernel choice (rt_internal.h resolve_variant / static_variant): what each requested variant becomes.
+// Unless a row says otherwise: 64 spp, depth 8, XORWOW, small flat tables present, 16-bit references, BVH depth 10.
+static void variant_fallback() {
+    const int unsupported = -100;  // (stands for RT_ERR_UNSUPPORTED in the `want` column)
+    struct Case {
+        int variant;
+        uint32_t spp, max_depth;
+        bool philox, prims_flat;
+        size_t flat_tab_bytes;
+        bool wide_refs;
+        uint32_t bvh_depth;
+        int want;
+        bool want_wide;
+    };
+    const size_t small = 1024, kb16 = 16 * 1024;
+    const Case cases[] = {
+        // compact parking needs spp < 8192, depth < 64 and spp · depth < 8192
+        {3, 8192, 1, false, true, small, false, 10, 2, false},
+        {3, 100, 100, false, true, small, false, 10, 2, false},
+        {3, 64, 64, false, true, small, false, 10, 2, false},
+        {3, 1023, 8, false, true, small, false, 10, 3, false},
+        // the flat kernels need the flat tables, the persistent one at most 16 KB of them
+        {5, 64, 8, false, false, 0, false, 10, 3, false},
+        {5, 8192, 1, false, false, 0, false, 10, 2, false},
+        {6, 64, 8, false, true, kb16 + 16, false, 10, 4, false},
+        {6, 64, 8, false, true, kb16, false, 10, 6, false},
+        // the persistent kernels assume every pixel traces a ray
+        {6, 0, 8, false, true, small, false, 10, 5, false},
+        {6, 0, 8, false, false, 0, false, 10, 3, false},
+        {4, 64, 0, false, true, small, false, 10, 3, false},
+        {4, 0, 64, false, true, small, false, 10, 2, false},
+        // v1 / v2 have no Philox build
+        {0, 64, 8, true, true, small, false, 10, 3, false},
+        {1, 64, 8, true, true, small, false, 10, 3, false},
+        {1, 8192, 1, true, true, small, false, 10, 2, false},
+        // 32-bit references: the wide builds of 3 and 4; for 2, v2 up to BVH depth 25 and v1 beyond
+        {3, 64, 8, false, true, small, true, 10, 3, true},
+        {4, 64, 8, false, true, small, true, 10, 4, true},
+        {2, 64, 8, false, true, small, true, 25, 1, false},
+        {2, 64, 8, false, true, small, true, 26, 0, false},
+        {2, 64, 8, true, true, small, true, 10, unsupported, false},
+        {3, 8192, 1, false, true, small, true, 20, 1, false},
+        {0, 64, 8, true, true, small, true, 10, 3, true},
+        // v2's LDS stack of 24 entries holds a BVH of depth 25
+        {1, 64, 8, false, true, small, false, 25, 1, false},
+        {1, 64, 8, false, true, small, false, 26, unsupported, false},
+        {1, 64, 8, false, true, small, false, 27, unsupported, false},
+    };
+    for (const Case& c : cases) {
+        const rt::VariantChoice r = rt::resolve_variant(
+            c.variant, rt::VariantFacts{c.spp, c.max_depth, c.philox, c.prims_flat, c.flat_tab_bytes, c.wide_refs, c.bvh_depth});
+        const bool ok = c.want == unsupported ? r.status == RT_ERR_UNSUPPORTED && !r.error.empty()
+                                              : r.status == RT_OK && r.variant == c.want && r.wide == c.want_wide;
+        if (!ok)
+            std::fprintf(stderr, "variant %d (case %d): got variant %d wide %d status %d\n", c.variant,
+                         (int)(&c - cases), r.variant, (int)r.wide, r.status);
+        CHECK(ok);
+    }
+    // the automatic choice before any timing: persistent below 32 spp; the flat pair up to RT_TUNE_FLAT_MAX primitives
+    CHECK(rt::static_variant(31, false, 488, 16) == 4 && rt::static_variant(32, false, 488, 16) == 3);
+    CHECK(rt::static_variant(31, true, 16, 16) == 6 && rt::static_variant(32, true, 16, 16) == 5);
+    CHECK(rt::static_variant(31, true, 17, 16) == 4 && rt::static_variant(32, true, 17, 16) == 3);
+}
+
 int main() {
+    variant_fallback();
     node_reference_payload();
     builtin_scenes();
     invalid_scenes();

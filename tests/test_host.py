@@ -246,6 +246,73 @@ def test_queue_knobs_defaults_and_ranges():
 QUEUE_PREFETCH_DEFAULT = 32
 QUEUE_GUIDE_DEFAULT = 0
 
+# rt_set_tuning's contract, one row per rt_tuning_key in the enum's order: name, default, lowest, highest, step
+# ("pow2": powers of two), and what rt_last_error() says after a refusal
+KNOBS = [
+    ("REGEN_THRESHOLD", 56, 1, 64, 1, "rt_set_tuning: regen threshold must be in [1, 64]"),
+    ("LEAF_MAX", 4, 1, 4, 1, "rt_set_tuning: leaf max must be in [1, 4]"),
+    ("PERSISTENT_WAVES", 0, 0, 16, 1, "rt_set_tuning: persistent waves per SIMD must be in [0, 16]"),
+    ("SAH_TRAVERSAL", 16, 1, 1000, 1, "rt_set_tuning: SAH traversal cost (x10) must be in [1, 1000]"),
+    ("LDS_PAD", 0, 0, 65536, 4, "rt_set_tuning: LDS pad must be a multiple of 4 in [0, 65536]"),
+    ("ADAPTIVE_ORDER", 1, 0, 1, 1, "rt_set_tuning: adaptive order must be 0 or 1"),
+    ("TEXEL_LAYOUT", 3, 3, 4, 1, "rt_set_tuning: texel layout must be 3 (RGB8) or 4 (RGBA8)"),
+    ("QUEUE_CHUNK", 128, 64, 4096, 64, "rt_set_tuning: queue chunk must be a multiple of 64 in [64, 4096]"),
+    ("QUEUE_STRIDE", 128, 128, 4096, "pow2",
+     "rt_set_tuning: queue head stride must be a power of two in [128, 4096] bytes"),
+    ("REGEN_LIVE_FRAC", 48, 0, 64, 1, "rt_set_tuning: live fraction must be in [0, 64]"),
+    ("LEAF_BREAK", 3, 0, 64, 1, "rt_set_tuning: leaf break must be in [0, 64]"),
+    ("RIUS_TRIPS", 4, 0, 64, 1, "rt_set_tuning: RandomInUnitSphere trips must be in [0, 64]"),
+    ("FLAT_MAX", 16, 0, 64, 1, "rt_set_tuning: flat kernel primitive limit must be in [0, 64]"),
+    ("QUEUE_PREFETCH", 32, 0, 64, 1, "rt_set_tuning: queue prefetch must be in [0, 64]"),
+    ("QUEUE_GUIDE", 0, 0, 64, 1, "rt_set_tuning: queue guide factor must be in [0, 64]"),
+    ("QUEUE_MIN_CHUNK", 16, 16, 64, 16, "rt_set_tuning: guided chunk floor must be 16, 32, 48 or 64"),
+    ("RIUS_TRIPS_PERSISTENT", 0, 0, 64, 1, "rt_set_tuning: RandomInUnitSphere trips must be in [0, 64]"),
+    ("PREFETCH_STOP", 8, 0, 1024, 1, "rt_set_tuning: prefetch stop must be in [0, 1024]"),
+    ("PERSISTENT_GROUP", 2, 0, 2, 1, "rt_set_tuning: persistent group must be 0, 1 or 2"),
+    ("GROUP_TAIL", 0, 0, 1000, 1, "rt_set_tuning: group tail must be in [0, 1000] permille"),
+    ("GROUP_ORDER", 0, 0, 1, 1, "rt_set_tuning: group order must be 0 or 1"),
+    ("QUEUE_RESET", 0, 0, 1, 1, "rt_set_tuning: queue reset must be 0 or 1"),
+    ("GROUP_CHUNK", 1024, 64, 4096, 64, "rt_set_tuning: group chunk must be a multiple of 64 in [64, 4096]"),
+    ("GROUP_LINGER_US", 0, 0, 100000, 1, "rt_set_tuning: group linger must be in [0, 100000] us"),
+    ("GROUP_WAVES", 16, 4, 16, 4, "rt_set_tuning: group waves must be 4, 8, 12 or 16"),
+    ("TILE_ENTRIES", 1, 0, 1, 1, "rt_set_tuning: tile entries must be 0 or 1"),
+    ("CAMERA_RESOLVE", 1, 0, 32, 1, "rt_set_tuning: camera resolve must be 0, 1 or a primitive cap in [2, 32]"),
+    ("PATH_END_STEP", 1, 0, 1, 1, "rt_set_tuning: path end step must be 0 or 1"),
+]
+
+
+def test_every_tuning_knob_default_range_and_refusal():
+    """rt_set_tuning over all of rt_tuning_key (CPU: no kernel runs): the default comes back from the first set, the
+    set value from the restore, both ends of the range are accepted, one step outside either end (and off the step,
+    and 192 for the power-of-two stride) is refused with the knob's own message and leaves the knob as it was; keys
+    outside the enum are refused as unknown."""
+    L = lib()
+    assert len(KNOBS) == 28
+
+    def refused(key, value, message):
+        assert abi.STATUS.get(L.rt_set_tuning(key, value)) == "RT_ERR_INVALID_ARGUMENT", (key, value)
+        assert L.rt_last_error().decode() == message, (key, value)
+
+    for key, (name, default, lo, hi, step, message) in enumerate(KNOBS):
+        assert getattr(abi, "RT_TUNE_" + name) == key
+        other = lo if default != lo else hi
+        assert L.rt_set_tuning(key, other) == default, name
+        assert L.rt_set_tuning(key, default) == other, name
+        assert L.rt_set_tuning(key, lo) == default, name
+        assert L.rt_set_tuning(key, hi) == lo, name
+        assert L.rt_set_tuning(key, default) == hi, name
+        bad = [lo - 1, hi + 1]
+        if step == "pow2":
+            bad.append(192)
+        elif step > 1:
+            bad.append(lo + 1)
+        for value in bad:
+            refused(key, value, message)
+        assert L.rt_set_tuning(key, default) == default, name  # unchanged by the refused values
+    for key in (-1, 28):
+        assert abi.STATUS.get(L.rt_set_tuning(key, 1)) == "RT_ERR_INVALID_ARGUMENT", key
+        assert "unknown key" in L.rt_last_error().decode()
+
 
 # ---------------------------------------------------------------------------------------------------
 # Image loading (LoadImage, Utils/RawStbImage.h:11-22) and the reference's own texture assets

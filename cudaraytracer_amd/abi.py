@@ -28,8 +28,8 @@ RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
 RT_TEMPORAL_RESET = 1 << 1
 # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host;
 # 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP; 13: rt_temporal_moments, rt_denoise_variance,
-# rt_denoise_variance_scratch_bytes
-ABI_VERSION = 13
+# rt_denoise_variance_scratch_bytes; 14: rt_query_rays, 32-bit references in rt_gbuffer and rt_trace_rays
+ABI_VERSION = 14
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
 MOTION_IDENTITY = (0.0, 0.0, 0.0, 1.0)
@@ -187,6 +187,22 @@ class GBufferArgs(C.Structure):
         ("reserved", C.c_uint32 * 2),
         ("tiling", Tiling),
         ("inputs", InputStruct),
+    ]
+
+
+class QueryArgs(C.Structure):  # rt_query_args
+    _fields_ = [
+        ("rays", C.c_void_p),
+        ("normal_depth", C.c_void_p),
+        ("albedo", C.c_void_p),
+        ("prim_id", C.c_void_p),
+        ("uv", C.c_void_p),
+        ("material", C.c_void_p),
+        ("hits", C.c_void_p),
+        ("n", C.c_uint32),
+        ("rays_per_lane", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
     ]
 
 

@@ -2584,31 +2584,32 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
 // threshold and leaf-break rules) without the shading — a wave owns `per_wave` consecutive rays of the batch and a
 // lane whose ray is done takes the wave's next one (ballot + mbcnt on a wave-uniform counter).  Rays are
 // (origin, -), (direction, -) float4 pairs; out[i] = (primitive index in the scene's BVH order or -1, t bits).
+// WIDE: the build for scenes with 32-bit references (RefW).
 // For measuring how ray order changes traversal cost (tools/coherence.py: a frame's bounce-2 rays in generation
 // order and sorted), and as a closest-hit query for callers that shade on their own.
-template <bool COUNT_TESTS>
+template <bool COUNT_TESTS, bool WIDE = false>
 __global__ __launch_bounds__(64, 8) void trace_rays_kernel(const KParams P, const float4* __restrict__ rays,
                                                           const uint32_t n_rays, const uint32_t per_wave,
                                                           int2* __restrict__ out) {
-    using Entry = uint16_t;
+    using Entry = typename RefW<WIDE>::Entry;
     extern __shared__ float4 lds[];
     const uint32_t lane = threadIdx.x & 63u;
     Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
     const __amdgpu_buffer_rsrc_t nrsrc =
         __builtin_amdgcn_make_buffer_rsrc((void*)P.nodes48, (short)0, (int)(P.num_nodes * 48u), 0x00020000);
-    stk[0] = (Entry)RefW<false>::kSentinel;
-    stk[64] = (Entry)RefW<false>::kSentinel;
+    stk[0] = (Entry)RefW<WIDE>::kSentinel;
+    stk[64] = (Entry)RefW<WIDE>::kSentinel;
     const uint32_t base = blockIdx.x * per_wave;
     const uint32_t end = min(base + per_wave, n_rays);
     Counts cnt{0, 0, 0, 0, 0, 0, 0};
-    Cursor c{(int)RefW<false>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
     uint32_t ray = base + lane, nrays = 0u;
     f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro;
     const auto start = [&](uint32_t i) {
         const float4 o = rays[2 * (size_t)i], d = rays[2 * (size_t)i + 1];
         ro = xyz(o);
         rd = xyz(d);
-        v3_start_trace<false>(P.num_nodes, c, nrays);
+        v3_start_trace<WIDE>(P.num_nodes, c, nrays);
     };
     if (ray < end) start(ray);
     uint32_t next = base + 64u;  // wave-uniform
@@ -2616,7 +2617,7 @@ __global__ __launch_bounds__(64, 8) void trace_rays_kernel(const KParams P, cons
         if (c.mode == MODE_TRAV) {
             uint32_t thr = P.regen_threshold;
             if (P.regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P.regen_live_frac) >> 6);
-            v3_traverse<COUNT_TESTS, NODES_48, 0u, false, false>(nrsrc, P.nodes48, P.refs, P.prims, stk, thr, ro, rd, c, cnt, 64u,
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P.nodes48, P.refs, P.prims, stk, thr, ro, rd, c, cnt, 64u,
                                                            P.leaf_break);
         }
         if (c.mode == MODE_SHADE) {
@@ -3739,8 +3740,8 @@ __device__ __forceinline__ void curand_init_state(unsigned long long seed, uint3
 
 // ---------------------------------------------------------------------------------------------------
 // First-hit G-buffer (rt_gbuffer): one wave per 8×8 pixel tile as v3, one camera ray per pixel through the pixel
-// centre, no RNG, no regeneration or persistence.  BVH scenes: v3's traversal on 16-bit LDS stacks run to completion
-// (threshold 0), as trace_rays_kernel; small scenes (those rt_render gives to the flat kernels): flat_trace over the
+// centre, no RNG, no regeneration or persistence.  BVH scenes: v3's traversal on LDS stacks (16-bit entries, or 32-bit
+// ones for scenes with wide references: WIDE) run to completion (threshold 0), as trace_rays_kernel; small scenes (those rt_render gives to the flat kernels): flat_trace over the
 // flat table.  Both return the geometric closest hit (rt_trace_rays' semantics: no reference replay).  The hit record
 // and the texture value follow shade().  The kernel's own arguments follow a KParams (the camera, tiling and scene
 // fields the shared device functions read).
@@ -3765,32 +3766,23 @@ __device__ __forceinline__ void camera_ray_at(PP P, const Camera& cam, const flo
     rd = normalize(sub(second, start));
 }
 
-// The pixel's three records from its closest hit (hit: index into K.prims or -1; tag: type | material << 4).
-__device__ __forceinline__ void gbuffer_store(const GBufParams& G, const size_t pix, const int hit, const uint32_t tag,
-                                              const float t, const f3 ro, const f3 rd) {
-    const KParams* P = &G.K;
-    if (hit < 0) {  // sky (Kernel.cu:41-44), as shade()
-        const float len = length(rd);
-        float q;
-        if (in_rcp_range(len)) q = div_rn(rd.y, len, rcp_rn(len));
-        else q = rd.y / len;
-        const float tt = 0.5f * (q + 1.0f);
-        const f3 c = add(scale(1.0f - tt, mk(P->bg0[0], P->bg0[1], P->bg0[2])), scale(tt, mk(P->bg1[0], P->bg1[1], P->bg1[2])));
-        if (G.normal_depth) G.normal_depth[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-        if (G.albedo) G.albedo[pix] = make_float4(c.x, c.y, c.z, 1.0f);
-        if (G.prim_id) G.prim_id[pix] = -1;
-        return;
-    }
+// The record of a closest hit, as shade() derives it (hit: index into P->prims, >= 0; tag: type | material << 4): the
+// HitRecord normal, the surface's (u, v) and the material's texture value there.  One copy for rt_gbuffer's planes and
+// rt_query_rays' records.  SPHERE_UV: GetSphereUV for every sphere (a query's uv output); otherwise only where the
+// texture reads it, as shade().
+template <bool SPHERE_UV>
+__device__ __forceinline__ void first_hit_record(const KParams* P, const int hit, const uint32_t tag, const float t,
+                                                 const f3 ro, const f3 rd, f3& normal, f3& alb, float& hu, float& hv) {
     const float4 p0 = P->prims[2 * hit + 0], p1 = P->prims[2 * hit + 1];
     const uint32_t type = tag & 15u, mat = tag >> 4;
     const float4 m0 = P->mats[3 * mat + 0];
     const uint32_t mtype = __float_as_uint(m0.x) & 15u, ttype = (__float_as_uint(m0.x) >> 4) & 15u;
-    f3 p, normal;
-    float hu = 0.0f, hv = 0.0f;
+    f3 p;
+    hu = 0.0f, hv = 0.0f;
     if (type == RT_SPHERE) {  // hit record of Sphere::Hit (Hittable.cuh:91-95)
         p = add(ro, scale(t, rd));
         normal = divs_rn(sub(p, xyz(p0)), p0.w, p1.y);
-        if (ttype == RT_IMAGE && mtype != RT_DIELECTRIC) {  // GetSphereUV (Hittable.cuh:119-125)
+        if (SPHERE_UV || (ttype == RT_IMAGE && mtype != RT_DIELECTRIC)) {  // GetSphereUV (Hittable.cuh:119-125)
             const float theta = rt_acosf(-normal.y);
             const float phi = rt_atan2f(-normal.z, normal.x) + 3.141592654f;
             hu = fdiv(phi, 2 * 3.141592654f);
@@ -3810,7 +3802,7 @@ __device__ __forceinline__ void gbuffer_store(const GBufParams& G, const size_t 
         normal = front ? outward : neg(outward);
         p = add(ro, scale(t, rd));
     }
-    f3 alb = mk(1.0f, 1.0f, 1.0f);  // Dielectric::Scatter's attenuation (Material.cuh:112)
+    alb = mk(1.0f, 1.0f, 1.0f);  // Dielectric::Scatter's attenuation (Material.cuh:112)
     if (mtype != RT_DIELECTRIC) {
         const float4 m1 = P->mats[3 * mat + 1];
         alb = xyz(m1);
@@ -3820,12 +3812,33 @@ __device__ __forceinline__ void gbuffer_store(const GBufParams& G, const size_t 
         }
         if (mtype == RT_DIFFUSELIGHT) alb = scale(m0.z, alb);  // DiffuseLight::Emitted (Material.cuh:164-176)
     }
+}
+
+// The pixel's three records from its closest hit (hit: index into K.prims or -1; tag: type | material << 4).
+__device__ __forceinline__ void gbuffer_store(const GBufParams& G, const size_t pix, const int hit, const uint32_t tag,
+                                              const float t, const f3 ro, const f3 rd) {
+    const KParams* P = &G.K;
+    if (hit < 0) {  // sky (Kernel.cu:41-44), as shade()
+        const float len = length(rd);
+        float q;
+        if (in_rcp_range(len)) q = div_rn(rd.y, len, rcp_rn(len));
+        else q = rd.y / len;
+        const float tt = 0.5f * (q + 1.0f);
+        const f3 c = add(scale(1.0f - tt, mk(P->bg0[0], P->bg0[1], P->bg0[2])), scale(tt, mk(P->bg1[0], P->bg1[1], P->bg1[2])));
+        if (G.normal_depth) G.normal_depth[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        if (G.albedo) G.albedo[pix] = make_float4(c.x, c.y, c.z, 1.0f);
+        if (G.prim_id) G.prim_id[pix] = -1;
+        return;
+    }
+    f3 normal, alb;
+    float hu, hv;
+    first_hit_record<false>(P, hit, tag, t, ro, rd, normal, alb, hu, hv);
     if (G.normal_depth) G.normal_depth[pix] = make_float4(normal.x, normal.y, normal.z, t);
     if (G.albedo) G.albedo[pix] = make_float4(alb.x, alb.y, alb.z, 1.0f);
     if (G.prim_id) G.prim_id[pix] = G.source[hit];
 }
 
-template <bool FLAT>
+template <bool FLAT, bool WIDE = false>
 __global__ __launch_bounds__(64, 4) void gbuffer_kernel(const GBufParams G) {
     const KParams* P = &G.K;
     // every lane traces a ray (a partial tile's outside lanes trace their off-image pixel's and store nothing), so
@@ -3847,19 +3860,19 @@ __global__ __launch_bounds__(64, 4) void gbuffer_kernel(const GBufParams G) {
         flat_trace<false>(P->prims, P->ref_nodes, P->flat_boxes, P->num_prims, P->flat_runs[0], P->flat_runs[1], ro, rd, hit,
                           tag, t, cnt, replay);
     } else {
-        using Entry = uint16_t;
+        using Entry = typename RefW<WIDE>::Entry;
         extern __shared__ float4 lds[];
         Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
         const __amdgpu_buffer_rsrc_t nrsrc =
             __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
-        stk[0] = (Entry)RefW<false>::kSentinel;
-        stk[64] = (Entry)RefW<false>::kSentinel;
-        Cursor c{(int)RefW<false>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+        stk[0] = (Entry)RefW<WIDE>::kSentinel;
+        stk[64] = (Entry)RefW<WIDE>::kSentinel;
+        Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
         uint32_t nrays = 0u;
-        v3_start_trace<false>(P->num_nodes, c, nrays);
+        v3_start_trace<WIDE>(P->num_nodes, c, nrays);
         while (__ballot(c.mode == MODE_TRAV) != 0) {
             if (c.mode == MODE_TRAV)
-                v3_traverse<false, NODES_48, 0u, false, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, 0u, ro, rd, c, cnt, 64u,
+                v3_traverse<false, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, 0u, ro, rd, c, cnt, 64u,
                                                                P->leaf_break);
         }
         hit = c.hit;
@@ -3867,6 +3880,100 @@ __global__ __launch_bounds__(64, 4) void gbuffer_kernel(const GBufParams G) {
         t = c.t_best;
     }
     if (inside) gbuffer_store(G, pix, hit, tag, t, ro, rd);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Ray queries with hit records (rt_query_rays): trace_rays_kernel's schedule — a wave owns `per_wave` consecutive rays
+// of the caller's batch, a lane whose ray is done writes its record and takes the wave's next one (ballot + mbcnt on
+// a wave-uniform counter) — with rt_gbuffer's record (first_hit_record) per ray.  Every output is optional; each
+// element is written by the one lane that traced the ray, so the result does not depend on the schedule.
+// ---------------------------------------------------------------------------------------------------
+struct QueryParams {
+    KParams K;
+    const float4* rays;
+    float4* normal_depth;
+    float4* albedo;
+    int32_t* prim_id;
+    float2* uv;
+    int32_t* material;
+    int2* hits;
+    const int32_t* source;  // as GBufParams.source
+    uint32_t n, per_wave;
+};
+
+// Ray i's records from its closest hit (hit: index into K.prims or -1; tag: type | material << 4).
+__device__ __forceinline__ void query_store(const QueryParams& Q, const size_t i, const int hit, const uint32_t tag,
+                                            const float t, const f3 ro, const f3 rd) {
+    if (Q.hits) Q.hits[i] = make_int2(hit, __float_as_int(t));  // trace_rays_kernel's pair
+    if (hit < 0) {  // (no camera: no sky)
+        if (Q.normal_depth) Q.normal_depth[i] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        if (Q.albedo) Q.albedo[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (Q.prim_id) Q.prim_id[i] = -1;
+        if (Q.uv) Q.uv[i] = make_float2(0.0f, 0.0f);
+        if (Q.material) Q.material[i] = -1;
+        return;
+    }
+    if (Q.prim_id) Q.prim_id[i] = Q.source[hit];
+    if (Q.material) Q.material[i] = (int32_t)(tag >> 4);
+    if (!Q.normal_depth && !Q.albedo && !Q.uv) return;  // (launch-uniform: a hits / pick / material query)
+    f3 normal, alb;
+    float hu, hv;
+    first_hit_record<true>(&Q.K, hit, tag, t, ro, rd, normal, alb, hu, hv);
+    if (Q.normal_depth) Q.normal_depth[i] = make_float4(normal.x, normal.y, normal.z, t);
+    if (Q.albedo) Q.albedo[i] = make_float4(alb.x, alb.y, alb.z, 1.0f);
+    if (Q.uv) Q.uv[i] = make_float2(hu, hv);
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(64, 4) void query_rays_kernel(const QueryParams Q) {
+    using Entry = typename RefW<WIDE>::Entry;
+    const KParams* P = &Q.K;
+    extern __shared__ float4 lds[];
+    const uint32_t lane = threadIdx.x & 63u;
+    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
+    const __amdgpu_buffer_rsrc_t nrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+    stk[0] = (Entry)RefW<WIDE>::kSentinel;
+    stk[64] = (Entry)RefW<WIDE>::kSentinel;
+    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
+    const uint32_t count = min(Q.n - base, Q.per_wave);  // rays of this wave's range (base + per_wave may wrap)
+    Counts cnt{0, 0, 0, 0, 0, 0, 0};
+    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+    uint32_t ray = base + lane, nrays = 0u;
+    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro;
+    const auto start = [&](uint32_t i) {
+        const float4 o = Q.rays[2 * (size_t)i], d = Q.rays[2 * (size_t)i + 1];
+        ro = xyz(o);
+        rd = xyz(d);
+        v3_start_trace<WIDE>(P->num_nodes, c, nrays);
+    };
+    if (lane < count) start(ray);
+    uint32_t taken = 64u;  // wave-uniform: rays of the wave's range handed out so far
+    while (__ballot(c.mode != MODE_DONE) != 0) {
+        if (c.mode == MODE_TRAV) {
+            uint32_t thr = P->regen_threshold;
+            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
+            v3_traverse<false, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c, cnt, 64u,
+                                                          P->leaf_break);
+        }
+        if (c.mode == MODE_SHADE) {
+            query_store(Q, ray, c.hit, c.tag, c.t_best, ro, rd);
+            c.mode = MODE_NEED;
+        }
+        const uint64_t needm = __ballot(c.mode == MODE_NEED);
+        if (needm != 0) {
+            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
+            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
+            if (c.mode == MODE_NEED) {
+                if (k < count) {
+                    ray = base + k;
+                    start(ray);
+                } else {
+                    c.mode = MODE_DONE;
+                }
+            }
+        }
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void render_init_kernel(uint32_t* state, uint32_t width, uint32_t local_rows,
@@ -4622,13 +4729,17 @@ int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* input
     return RT_OK;
 }
 
+// rt_trace_rays' automatic rays per lane: enough waves to fill the device (8 per SIMD), at most 16 rays per lane
+static uint32_t auto_rays_per_lane(const uint32_t n) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, (uint64_t)n / (64ull * 8192ull)));
+}
+
 int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t* hits, uint64_t* counters,
                   int count_tests, rt_stream stream) {
     if (!scene || (n && (!rays || !hits))) { set_error("rt_trace_rays: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
     if (n == 0) return RT_OK;
     const DeviceScene& S = scene->dev;
-    if (S.wide_refs) { set_error("rt_trace_rays: scenes with 32-bit references are not supported"); return RT_ERR_UNSUPPORTED; }
-    const size_t lds = (size_t)(S.depth + 2) * 64 * 2;
+    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
     if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_trace_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
     dev::KParams P;
     std::memset(&P, 0, sizeof(P));
@@ -4637,18 +4748,14 @@ int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t*
     P.regen_threshold = (uint32_t)g_regen_threshold;
     P.regen_live_frac = (uint32_t)g_regen_live_frac;
     P.leaf_break = (uint32_t)g_leaf_break;
-    // rays per wave: enough waves to fill the device (8 per SIMD), at most 16 rays per lane
-    const uint32_t per_lane = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, (uint64_t)n / (64ull * 8192ull)));
-    const uint32_t per_wave = 64u * per_lane;
+    const uint32_t per_wave = 64u * auto_rays_per_lane(n);
     const uint32_t grid = (uint32_t)(((uint64_t)n + per_wave - 1) / per_wave);
     hipStream_t s = (hipStream_t)stream;
     (void)hipGetLastError();
-    if (count_tests && counters)
-        hipLaunchKernelGGL(dev::trace_rays_kernel<true>, dim3(grid), dim3(64), lds, s, P, (const float4*)rays, n, per_wave,
-                           (int2*)hits);
-    else
-        hipLaunchKernelGGL(dev::trace_rays_kernel<false>, dim3(grid), dim3(64), lds, s, P, (const float4*)rays, n, per_wave,
-                           (int2*)hits);
+    const bool count = count_tests && counters;
+    const auto kernel = S.wide_refs ? (count ? dev::trace_rays_kernel<true, true> : dev::trace_rays_kernel<false, true>)
+                                    : (count ? dev::trace_rays_kernel<true, false> : dev::trace_rays_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, P, (const float4*)rays, n, per_wave, (int2*)hits);
     return hip_check(hipGetLastError(), "rt_trace_rays: kernel launch", RT_ERR_LAUNCH);
 }
 
@@ -4664,10 +4771,9 @@ int rt_gbuffer(const rt_scene* scene, const rt_gbuffer_args* a, rt_stream stream
     if (rc == RT_OK) rc = check_last_row("rt_gbuffer", T, a->height);
     if (rc != RT_OK) return rc;
     const DeviceScene& S = scene->dev;
-    if (S.wide_refs) { set_error("rt_gbuffer: scenes with 32-bit references are not supported"); return RT_ERR_UNSUPPORTED; }
     // the scenes rt_render's automatic choice gives to the flat kernels
     const bool flat = S.prims_flat && S.flat_source && S.num_prims <= (uint32_t)g_flat_max;
-    const size_t lds = flat ? 0 : (size_t)(S.depth + 2) * 64 * 2;
+    const size_t lds = flat ? 0 : (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
     if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_gbuffer: BVH too deep"); return RT_ERR_UNSUPPORTED; }
     dev::GBufParams G;
     std::memset(&G, 0, sizeof(G));
@@ -4688,9 +4794,64 @@ int rt_gbuffer(const rt_scene* scene, const rt_gbuffer_args* a, rt_stream stream
     (void)hipGetLastError();
     if (flat)
         hipLaunchKernelGGL(dev::gbuffer_kernel<true>, dim3((uint32_t)tiles), dim3(64), 0, s, G);
+    else if (S.wide_refs)
+        hipLaunchKernelGGL((dev::gbuffer_kernel<false, true>), dim3((uint32_t)tiles), dim3(64), lds, s, G);
     else
         hipLaunchKernelGGL(dev::gbuffer_kernel<false>, dim3((uint32_t)tiles), dim3(64), lds, s, G);
     return hip_check(hipGetLastError(), "rt_gbuffer: kernel launch", RT_ERR_LAUNCH);
+}
+
+int rt_query_rays(const rt_scene* scene, const rt_query_args* a, rt_stream stream) {
+    // (every argument check runs before the first device call)
+    const auto bad = [](const char* what) {
+        set_error(std::string("rt_query_rays: ") + what);
+        return RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!a) return bad("NULL args");
+    if (a->flags != 0 || a->reserved != 0) return bad("flags and reserved must be 0");
+    if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
+    const uint64_t n = a->n;
+    const void* const outs[6] = {a->normal_depth, a->albedo, a->prim_id, a->uv, a->material, a->hits};
+    const uint64_t out_bytes[6] = {n * 16u, n * 16u, n * 4u, n * 8u, n * 4u, n * 8u};
+    bool any = false;
+    for (int o = 0; o < 6; o++) any = any || outs[o] != nullptr;
+    if (!any) return bad("no output buffer");
+    if (n == 0) return RT_OK;  // nothing to trace
+    if (!a->rays) return bad("NULL rays");
+    for (int o = 0; o < 6; o++) {
+        if (overlaps(outs[o], out_bytes[o], a->rays, n * 32u)) return bad("an output overlaps rays");
+        for (int p = 0; p < o; p++)
+            if (overlaps(outs[o], out_bytes[o], outs[p], out_bytes[p])) return bad("outputs overlap each other");
+    }
+    if (!scene) return bad("NULL scene");
+    const DeviceScene& S = scene->dev;
+    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
+    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_query_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    dev::QueryParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    dev::KParams& P = Q.K;
+    fill_scene_tables(P, S);
+    P.regen_threshold = (uint32_t)g_regen_threshold;
+    P.regen_live_frac = (uint32_t)g_regen_live_frac;
+    P.leaf_break = (uint32_t)g_leaf_break;
+    Q.rays = (const float4*)a->rays;
+    Q.normal_depth = (float4*)a->normal_depth;
+    Q.albedo = (float4*)a->albedo;
+    Q.prim_id = a->prim_id;
+    Q.uv = (float2*)a->uv;
+    Q.material = a->material;
+    Q.hits = (int2*)a->hits;
+    Q.source = (const int32_t*)S.prim_source;
+    Q.n = a->n;
+    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->n));
+    const uint32_t grid = (uint32_t)((n + Q.per_wave - 1) / Q.per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    if (S.wide_refs)
+        hipLaunchKernelGGL(dev::query_rays_kernel<true>, dim3(grid), dim3(64), lds, s, Q);
+    else
+        hipLaunchKernelGGL(dev::query_rays_kernel<false>, dim3(grid), dim3(64), lds, s, Q);
+    return hip_check(hipGetLastError(), "rt_query_rays: kernel launch", RT_ERR_LAUNCH);
 }
 
 int rt_set_pixel_cost(void* buffer, uint64_t bytes) {

@@ -55,6 +55,39 @@ class DeviceScene:
         check(lib().rt_scene_edit(self.handle, arr, len(arr), C.byref(new.handle)), "rt_scene_edit")
         return new
 
+    # rt_query_rays' outputs: name -> (trailing shape, dtype)
+    QUERY_OUTPUTS = {"normal_depth": ((4,), torch.float32), "albedo": ((4,), torch.float32), "prim_id": ((), torch.int32),
+                     "uv": ((2,), torch.float32), "material": ((), torch.int32), "hits": ((2,), torch.int32)}
+
+    def query(self, rays, outputs=("normal_depth", "albedo", "prim_id", "uv", "material", "hits"),
+              rays_per_lane: int = 0) -> dict:
+        """Closest hit and hit record of rays of the caller's own (rt_query_rays), asynchronous on torch's current
+        stream.  rays: (n, 2, 4) float32, (origin, -), (direction, -) per ray — a torch tensor on the device, or a numpy
+        array (uploaded to the current device).  Returns {name: tensor} for the outputs asked for: normal_depth (n, 4),
+        albedo (n, 4), prim_id (n,), uv (n, 2), material (n,), hits (n, 2) (include/rt_hip.h, rt_query_args)."""
+        names = tuple(outputs)
+        unknown = [o for o in names if o not in self.QUERY_OUTPUTS]
+        if unknown or not names or len(set(names)) != len(names):
+            raise ValueError(f"outputs must be distinct names out of {tuple(self.QUERY_OUTPUTS)}, not {names!r}")
+        if isinstance(rays, np.ndarray):
+            rays = torch.from_numpy(np.array(rays, dtype=np.float32, order="C")).cuda()  # (a copy: the caller's may be read-only)
+        if rays.dtype != torch.float32 or rays.dim() != 3 or tuple(rays.shape[1:]) != (2, 4) or not rays.is_cuda:
+            raise ValueError("rays must be a float32 (n, 2, 4) tensor on the device")
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        out = {o: torch.empty((n,) + self.QUERY_OUTPUTS[o][0], dtype=self.QUERY_OUTPUTS[o][1], device=rays.device)
+               for o in names}
+        if n == 0:
+            return out
+        a = abi.QueryArgs()
+        a.rays = rays.data_ptr()
+        for o in names:
+            setattr(a, o, out[o].data_ptr())
+        a.n, a.rays_per_lane = n, rays_per_lane
+        stream = torch.cuda.current_stream(rays.device).cuda_stream
+        check(lib().rt_query_rays(self.handle, C.byref(a), C.c_void_p(stream)), "rt_query_rays")
+        return out
+
     def close(self) -> None:
         if self.handle:
             lib().rt_scene_destroy(self.handle)

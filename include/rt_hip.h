@@ -184,8 +184,9 @@ const char* rt_version(void);
  * can refuse a newer library.  6: RT_COUNTERS_WORDS (24) counter words with RT_FLAG_COUNT_TESTS, rt_set_launch_flags.
  * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal.  9: rt_scene_motion, rt_temporal_dynamic,
  * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE.  12: RT_TUNE_PATH_END_STEP.
- * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes. */
-#define RT_ABI_VERSION 13
+ * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes.  14: rt_query_rays; rt_gbuffer and
+ * rt_trace_rays take scenes with 32-bit BVH references. */
+#define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
 /* hipSetDevice on the calling thread. */
@@ -382,9 +383,40 @@ int rt_set_ray_dump(void* rays, uint32_t capacity, uint32_t* count, uint32_t dep
  * (BVHNode::Hit semantics, Hittable.cuh:387-439; t in (0.001, FLT_MAX)): hits[2i] = the primitive's index in the
  * scene's BVH order or -1, hits[2i + 1] = the hit distance's bits.  counters: optional device uint64[RT_COUNTERS_WORDS]
  * ([0] rays; with count_tests also box and primitive tests and wave iterations, as rt_render).  Asynchronous on
- * `stream`.  Scenes with 32-bit references are not supported (RT_ERR_UNSUPPORTED). */
+ * `stream`.  Scenes of any size; a BVH deeper than 64 levels is refused (RT_ERR_UNSUPPORTED, "BVH too deep"). */
 int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t* hits, uint64_t* counters,
                   int count_tests, rt_stream stream);
+
+/* Closest hit of n rays of the caller's with rt_gbuffer's hit record per ray: rt_trace_rays' semantics (the geometric
+ * closest hit, t in (0.001, FLT_MAX), no reference replay), the record derived as rt_gbuffer / the render kernels
+ * derive it.  Every output is optional device memory of n elements, at least one must be given:
+ *   normal_depth  float4: rt_gbuffer's record (xyz = the HitRecord normal, w = t in units of |direction|: the point
+ *                 is origin + t · direction).  Miss: (0, 0, 0, -1).
+ *   albedo        float4: rt_gbuffer's value on a hit (w = 1).  Miss: (0, 0, 0, 0) (no camera: no sky).
+ *   prim_id       int32: the hittable's index in rt_scene_desc.hittables (rt_gbuffer's meaning).  Miss: -1.
+ *   uv            float2: GetSphereUV (Hittable.cuh:119-125) for every sphere, the rectangle's (u, v).  Miss: (0, 0).
+ *   material      int32: the hittable's index into rt_scene_desc.materials.  Miss: -1.
+ *   hits          int2: exactly what rt_trace_rays writes for the ray (index in BVH order or -1, t bits).
+ * rays_per_lane: 0 = automatic (rt_trace_rays' rule), 1..16: a wave owns 64 · rays_per_lane consecutive rays and a
+ * lane that finishes takes the wave's next one; the setting changes the schedule only, never a result.  One
+ * asynchronous launch on `stream`; every element is written by one lane, without atomics, so two calls give the same
+ * bits.  RT_ERR_INVALID_ARGUMENT, before any device call: NULL args, NULL rays with n > 0, no output buffer, an
+ * output that overlaps `rays` or another output, rays_per_lane above 16, non-zero flags or reserved.  n = 0: RT_OK.
+ * An empty scene gives all misses.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED ("BVH too deep"). */
+typedef struct rt_query_args {
+    const float* rays;      /* device, n x 2 float4: (origin, -), (direction, -), as rt_trace_rays */
+    float*   normal_depth;
+    float*   albedo;
+    int32_t* prim_id;
+    float*   uv;
+    int32_t* material;
+    int32_t* hits;
+    uint32_t n;
+    uint32_t rays_per_lane;
+    uint32_t flags;         /* must be 0 */
+    uint32_t reserved;      /* must be 0 */
+} rt_query_args;
+int rt_query_rays(const rt_scene* scene, const rt_query_args* args, rt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* First-hit G-buffer and edge-avoiding denoiser for low-spp frames.  The reference has neither: while */
@@ -404,8 +436,8 @@ int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t*
  *   prim_id       int32: the hit hittable's index in rt_scene_desc.hittables (inactive entries counted; for
  *                 rt_scene_from_reference_graph scenes the order of rt_reference_graph_flatten).  Miss: -1.
  *                 At the cursor's pixel this is an object pick.
- * A band render's rows equal the whole-frame rows (rt_tiling, as rt_render).  Scenes with 32-bit BVH references
- * are not supported (RT_ERR_UNSUPPORTED, as rt_trace_rays). */
+ * A band render's rows equal the whole-frame rows (rt_tiling, as rt_render).  Scenes of any size (16- or 32-bit BVH
+ * references); a BVH deeper than 64 levels is refused (RT_ERR_UNSUPPORTED, "BVH too deep", as rt_trace_rays). */
 typedef struct rt_gbuffer_args {
     float* normal_depth;
     float* albedo;

@@ -1,4 +1,7 @@
-"""Interleaved A/B timing of kernel variants on one config (one process, rounds interleaved)."""
+"""Interleaved A/B timing of kernel variants on one config (one process, rounds interleaved).
+
+--gbuffer N times rt_gbuffer on the config's frame instead (median of N calls after 5 warm-up calls, HIP events per call):
+with tools/ab_builds.sh and AB_EXTRA="--gbuffer 50", the pass under two builds of the library in alternation."""
 import argparse, os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -17,8 +20,21 @@ ap.add_argument("--pwaves", default="0", help="persistent grid waves/SIMD to try
 ap.add_argument("--regions", default="2", help="v5 tiles per region to try (RT_TUNE_REGION_TILES; a build with ab_src/v5_region_refill.patch)")
 ap.add_argument("--sah", default="16", help="SAH traversal costs x10 to try (RT_TUNE_SAH_TRAVERSAL)")
 ap.add_argument("--rng", default="xorwow", choices=("xorwow", "philox"))
+ap.add_argument("--gbuffer", type=int, default=0, help="time this many rt_gbuffer calls instead of rt_render")
 args = ap.parse_args()
 cfg = scenes.CONFIGS[args.config]
+if args.gbuffer:
+    ds, r, inp, t = DeviceScene(scenes.builtin(cfg.scene)), Renderer(cfg.width, cfg.height), cfg.inputs(), []
+    for i in range(5 + args.gbuffer):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r.gbuffer(ds, inp)
+        e1.record()
+        torch.cuda.synchronize()
+        t.append(e0.elapsed_time(e1))
+    t = t[5:]
+    print(f"{args.config} rt_gbuffer {cfg.width}x{cfg.height}: median {statistics.median(t):.4f} ms  min {min(t):.4f}  max {max(t):.4f}", flush=True)
+    sys.exit(0)
 if args.spp:
     cfg = cfg.scaled(cfg.width, cfg.height, args.spp)
 variants = []

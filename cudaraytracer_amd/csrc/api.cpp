@@ -13,6 +13,7 @@
 #include <unordered_set>
 
 #include "../../include/rt_reference_graph.h"
+#include "rt_bounce_entry.h"
 #include "rt_internal.h"
 #include "rt_scene_device.h"
 
@@ -72,6 +73,9 @@ static void free_device(DeviceScene* s) {
     if (s->bvh_boxes) (void)hipFree((void*)s->bvh_boxes);
     if (s->bvh_ref_pairs) (void)hipFree((void*)s->bvh_ref_pairs);
     s->bvh_ref_nodes = s->bvh_boxes = s->bvh_ref_pairs = nullptr;
+    if (s->leaf_records) (void)hipFree((void*)s->leaf_records);
+    if (s->bounce_grid) (void)hipFree((void*)s->bounce_grid);
+    s->leaf_records = s->bounce_grid = nullptr;
     if (s->prim_source) (void)hipFree((void*)s->prim_source);
     if (s->flat_source) (void)hipFree((void*)s->flat_source);
     s->prim_source = s->flat_source = nullptr;
@@ -116,6 +120,17 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     d.bvh_ref_pairs = p;
     d.flat_runs[0] = h.flat_runs[0];
     d.flat_runs[1] = h.flat_runs[1];
+    if (!h.bounce_grid.empty()) {
+        if ((rc = upload(h.leaf_records, &p, "hipMalloc/hipMemcpy(leaf_records)"))) goto fail;
+        d.leaf_records = p;
+        if ((rc = upload(h.bounce_grid, &p, "hipMalloc/hipMemcpy(bounce_grid)"))) goto fail;
+        d.bounce_grid = p;
+        for (int i = 0; i < 3; i++) {
+            d.grid_dim[i] = h.grid_dim[i];
+            d.grid_inv[i] = h.grid_inv[i];
+            d.grid_off[i] = h.grid_off[i];
+        }
+    }
     if ((rc = upload(h.prim_source, &p, "hipMalloc/hipMemcpy(prim_source)"))) goto fail;
     d.prim_source = p;
     if ((rc = upload(h.flat_source, &p, "hipMalloc/hipMemcpy(flat_source)"))) goto fail;
@@ -141,7 +156,7 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     d.has_rects = h.has_rects;
     d.device_bytes = (h.nodes.size() + h.nodes48.size() + h.refs.size() + h.prims.size() + h.prims_flat.size() + h.ref_nodes.size() +
                       h.flat_boxes.size() + h.flat_ref_pairs.size() + h.bvh_ref_nodes.size() + h.bvh_boxes.size() + h.bvh_ref_pairs.size() + h.mats.size() +
-                      h.prim_source.size() + h.flat_source.size()) * 4 +
+                      h.prim_source.size() + h.flat_source.size() + h.leaf_records.size()) * 4 + h.bounce_grid.size() * 2 +
                      h.imgs.size() * 4 + h.texels.size();
     *out = s;
     return RT_OK;
@@ -527,11 +542,55 @@ int rt_build_host_tables(const rt_scene_desc* desc, float* nodes, float* prims, 
     info->num_prims = h.num_prims;
     info->num_materials = h.num_mats;
     info->depth = h.depth;
-    if (nodes) std::copy(h.nodes.begin(), h.nodes.end(), nodes);
+    if (nodes) std::copy(h.nodes.begin(), h.nodes.begin() + (size_t)h.num_nodes * 16, nodes);
     // (num_prims records: an empty scene's table carries one zero record for the device, not for the caller)
     if (prims) std::copy(h.prims.begin(), h.prims.begin() + (size_t)h.num_prims * 8, prims);
     if (materials) std::copy(h.mats.begin(), h.mats.end(), materials);
     if (prim_source) std::copy(h.prim_source.begin(), h.prim_source.end(), prim_source);
+    return RT_OK;
+}
+
+int rt_bounce_entries_host(const rt_scene_desc* desc, float* chain_nodes, float* nodes48, uint32_t* refs,
+                           uint32_t* records, uint16_t* grid, rt_bounce_entries_info* info) {
+    if (!info) { set_error("rt_bounce_entries_host: info is NULL"); return RT_ERR_INVALID_ARGUMENT; }
+    HostScene h;
+    int rc = guarded("rt_bounce_entries_host", [&]() -> int {
+        std::string err;
+        int r = build_host_scene(desc, &h, &err);
+        if (r) set_error("rt_bounce_entries_host: " + err);
+        return r;
+    });
+    if (rc) return rc;
+    std::memset(info, 0, sizeof(*info));
+    info->num_nodes = h.num_nodes;
+    info->depth = h.depth;
+    if (h.bounce_grid.empty()) return RT_OK;  // no table: num_records = 0
+    info->num_chain_nodes = h.num_chain_nodes;
+    info->num_records = (uint32_t)(h.leaf_records.size() / 4);
+    for (int i = 0; i < 3; i++) {
+        info->grid_dim[i] = h.grid_dim[i];
+        info->grid_origin[i] = h.grid_origin[i];
+        info->grid_inv[i] = h.grid_inv[i];
+        info->grid_off[i] = h.grid_off[i];
+    }
+    if (chain_nodes) std::copy(h.chain_nodes.begin(), h.chain_nodes.end(), chain_nodes);
+    if (nodes48) std::copy(h.nodes48.begin(), h.nodes48.end(), nodes48);
+    if (refs) std::copy(h.refs.begin(), h.refs.end(), refs);
+    if (records) std::copy(h.leaf_records.begin(), h.leaf_records.end(), records);
+    if (grid) std::copy(h.bounce_grid.begin(), h.bounce_grid.end(), grid);
+    return RT_OK;
+}
+
+int rt_bounce_entry_cells(const rt_bounce_entries_info* info, const float* origins, uint32_t n, uint32_t* cells) {
+    if (!info || (n && (!origins || !cells))) { set_error("rt_bounce_entry_cells: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
+    if (info->num_records == 0 || !info->grid_dim[0] || !info->grid_dim[1] || !info->grid_dim[2]) {
+        set_error("rt_bounce_entry_cells: the scene has no bounce-entry table");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const float dimf[3] = {(float)(info->grid_dim[0] - 1u), (float)(info->grid_dim[1] - 1u), (float)(info->grid_dim[2] - 1u)};
+    for (uint32_t i = 0; i < n; i++)
+        cells[i] = bounce_cell(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2], info->grid_inv,
+                               info->grid_off, dimf, info->grid_dim);
     return RT_OK;
 }
 

@@ -284,6 +284,12 @@ struct KParams {
     uint32_t path_end_step;          // v3, with camera_resolve: in a wave whose record the pre-step scans, every path end
                                      // (and the pixel's first camera ray) goes through the pre-step: the lane waits in
                                      // MODE_ENDED with its contribution parked (0 = only cleared misses, RT_TUNE_PATH_END_STEP)
+    const uint4* bounce_records;     // v3 (16-bit references): per leaf its bounce-entry record (rt_bounce_entry.h), NULL =
+                                     // every bounce ray starts at the root (rt_set_bounce_entries(0), or no table)
+    const uint16_t* bounce_grid;     // ... per origin-grid cell the index of a record
+    float grid_inv[3], grid_off[3];  // ... a ray origin's cell coordinate: fma(o, inv, off) clamped to [0, grid_max]
+    float grid_max[3];               // ... dim - 1 per axis
+    uint32_t grid_nx, grid_ny;       // ... cell = (z * ny + y) * nx + x
 };
 
 constexpr int kStackMax = 64;
@@ -1768,6 +1774,42 @@ __device__ __forceinline__ void v3_start_camera_trace(KParamsC* q, const uint32_
     }
 }
 
+// A bounce ray (shade() returned SHADE_CONTINUE; v3_start_trace has run) moves its start from the root to a leaf near
+// its origin (rt_bounce_entry.h): the origin's grid cell names a leaf record, whose entry 0 becomes the lane's postponed
+// leaf, entry 1 its `node` and the rest its stack, the record's last reference at the bottom — the own leaf, then the
+// siblings along its ancestor path from the deepest up, two per chain node.  A "root" record, or a launch without the
+// table, keeps the root.  Per lane: one 2-byte and one 16-byte load and up to six LDS stores.
+// Exactness: as for v3_start_camera_trace.  Any leaf's record covers the whole tree with the same conservative box
+// tests (a chain node's boxes are copies of the real nodes'), so every primitive whose test can accept the ray is
+// tested and the geometric closest hit is the root traversal's; ties are flagged in any test order; bvh_clear /
+// ref_trace_wave read the hit record and the reference tables only.  The host has checked every record against the
+// stack's depth entries (scene_build.cpp).
+template <bool WIDE>
+__device__ __forceinline__ void v3_bounce_entry(KParamsC* q, typename RefW<WIDE>::Entry* const stk, const f3 ro, Cursor& c) {
+    if constexpr (!WIDE) {
+        const uint4* const recs = q->bounce_records;
+        if (!recs) return;  // (launch-uniform)
+        const float fx = fminf(fmaxf(__builtin_fmaf(ro.x, q->grid_inv[0], q->grid_off[0]), 0.0f), q->grid_max[0]);
+        const float fy = fminf(fmaxf(__builtin_fmaf(ro.y, q->grid_inv[1], q->grid_off[1]), 0.0f), q->grid_max[1]);
+        const float fz = fminf(fmaxf(__builtin_fmaf(ro.z, q->grid_inv[2], q->grid_off[2]), 0.0f), q->grid_max[2]);
+        const uint32_t cell = ((uint32_t)fz * q->grid_ny + (uint32_t)fy) * q->grid_nx + (uint32_t)fx;
+        const uint4 r = recs[q->bounce_grid[cell]];
+        const uint32_t e0 = r.x & 0xffffu;
+        if (e0 != kTileEntryRoot) {
+            c.leaf = (int)e0;
+            c.node = (int)(r.x >> 16);
+            const uint32_t e[6] = {r.y & 0xffffu, r.y >> 16, r.z & 0xffffu, r.z >> 16, r.w & 0xffffu, r.w >> 16};
+            uint32_t n = 0;
+#pragma unroll
+            for (int i = 0; i < 6; i++) n += e[i] != kTileEntryNone ? 1u : 0u;  // (packed from the front)
+#pragma unroll
+            for (int i = 0; i < 6; i++)
+                if ((uint32_t)i < n) stk[(kStackBase + n - 1u - (uint32_t)i) * 64] = (typename RefW<WIDE>::Entry)e[i];
+            c.sp = kStackBase + n;
+        }
+    }
+}
+
 // A path ended with `contrib`: accumulate (Kernel.cu:147), then the next sample's camera ray, or finish.
 template <bool WIDE, class R>
 __device__ __forceinline__ void v3_next_sample(const KParams& P, uint32_t x, uint32_t g, f3 contrib, R& rng,
@@ -2478,6 +2520,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
                 if (kparams_reload()->camera_resolve != 0u)
                     v3_resolve_camera<COUNT_TESTS, R, COMPACT>(x, g, tile, park, ro, rd, c, cnt);
             }
+            bool bounce = false;  // this pass's shade() continued the lane's path
             if (c.mode == MODE_SHADE) {
                 R rng;
                 f3 col, att;
@@ -2521,10 +2564,13 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
                     park[(PK_COL + 2) * 64] = __float_as_uint(col.z);
                 } else {
                     v3_start_trace<WIDE>(P.num_nodes, c, rays);
+                    bounce = true;
                     if (COUNT_TESTS && P.ray_dump) dump_ray(P, depth == P.ray_dump_depth, ro, rd);
                 }
                 v3_park<COMPACT, false>(park, rng, col, att, sample, depth, rays);
             }
+            // (behind the park: the path state is out of the registers when the record arrives)
+            if (bounce) v3_bounce_entry<WIDE>(kparams_reload(), stk, ro, c);
             // (RT_REPLAY_SAME_PASS: the lanes shade() returned SHADE_REPLAY for replay now, every lane active, and shade)
             if (!RT_REPLAY_SAME_PASS || __ballot(c.mode == MODE_REPLAY) == 0u) break;
             bvh_replay_wave(kparams_reload(), prims, c, ro, rd, cnt, COUNT_TESTS);
@@ -4125,6 +4171,9 @@ constexpr int kCameraResolveMax = 32;  // a record's eight references hold at mo
 // the depth limit, an emitter, a camera ray that missed) and the pixel's first camera ray go through the pre-step too:
 // no lane holds a camera ray's leaf chain through a traversal call; 0 = only cleared misses do (A/B, tests)
 thread_local int g_path_end_step = 1;
+// rt_set_bounce_entries: 1 (default) = the v3 kernels start a bounce ray at a leaf near its origin (rt_bounce_entry.h;
+// scenes with the table), 0 = at the root (A/B, tests)
+thread_local int g_bounce_entries = 1;
 
 // One row per rt_tuning_key, in the enum's order: where the value lives, the values rt_set_tuning accepts (lo..hi,
 // multiples of `step`, powers of two where `pow2`) and what it says when it refuses one.
@@ -4883,6 +4932,16 @@ int rt_set_variant(int variant) {
 
 int rt_last_variant(void) { return g_last_variant; }
 
+int rt_set_bounce_entries(int on) {
+    if (on != 0 && on != 1) {
+        set_error("rt_set_bounce_entries: the value must be 0 or 1");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const int prev = g_bounce_entries;
+    g_bounce_entries = on;
+    return prev;
+}
+
 int rt_set_tuning(int key, int value) {
     if (key < 0 || key >= (int)(sizeof(kKnobs) / sizeof(kKnobs[0]))) {
         set_error("rt_set_tuning: unknown key");
@@ -5168,6 +5227,20 @@ int bind_tile_entries(dev::KParams& P, const int kernel, const DeviceScene& S, h
     return RT_OK;
 }
 
+// v3 on a scene with the bounce-entry tables (rt_bounce_entry.h): bounce rays start at a leaf near their origin
+void bind_bounce_entries(dev::KParams& P, const int kernel, const DeviceScene& S) {
+    if (kernel != 3 || S.wide_refs || !g_bounce_entries || !S.leaf_records || !S.bounce_grid) return;
+    P.bounce_records = (const uint4*)S.leaf_records;
+    P.bounce_grid = (const uint16_t*)S.bounce_grid;
+    for (int i = 0; i < 3; i++) {
+        P.grid_inv[i] = S.grid_inv[i];
+        P.grid_off[i] = S.grid_off[i];
+        P.grid_max[i] = (float)(S.grid_dim[i] - 1u);
+    }
+    P.grid_nx = S.grid_dim[0];
+    P.grid_ny = S.grid_dim[1];
+}
+
 // What of KParams follows from the kernel: its LDS per wave, the flat kernels' tables, the tile grid
 void fill_kernel_params(dev::KParams& P, const Variant& V, const LaunchShape& L, const DeviceScene& S) {
     P.lds_wave_words = L.wave_words;
@@ -5245,6 +5318,7 @@ int rt_render(const rt_scene* scene, const rt_render_args* a, rt_stream stream) 
     std::unique_lock<std::mutex> entries_lock;
     rc = bind_tile_entries(P, V.kernel, S, s, &entries, &entries_lock);
     if (rc != RT_OK) return rc;
+    bind_bounce_entries(P, V.kernel, S);
 
     if (trial.timed) (void)hipEventRecord(trial.timed->ev[trial.slot], s);
     (void)hipGetLastError();

@@ -88,6 +88,16 @@ struct HostScene {
     std::vector<float> bvh_boxes;      // ... and per BVH-order primitive its reference box: (lo.xyz, 0), (hi.xyz, 0)
     std::vector<float> bvh_ref_pairs;  // ... and per reference node its two children: (lo.xyz, ref), (hi.xyz, 0) each
                                        // (a primitive child's box is not used) — the wave-serial replay's records
+    // Bounce entries (16-bit references only; rt_bounce_entry.h): chain nodes behind the num_nodes real ones in
+    // nodes48 / refs (not in `nodes`: only the v3 kernels' 48-B path visits them), one record per leaf, the origin grid
+    uint32_t num_chain_nodes = 0;
+    std::vector<float> chain_nodes;       // 16 floats per chain node in `nodes`' layout: its boxes before the packing
+    std::vector<uint32_t> leaf_records;   // 4 words per leaf, in the tree's depth-first order (TileRecord's form)
+    std::vector<uint16_t> bounce_grid;    // per cell the index of a leaf record; empty = no table
+    uint32_t grid_dim[3] = {0u, 0u, 0u};
+    float grid_origin[3] = {0.0f, 0.0f, 0.0f};
+    float grid_inv[3] = {0.0f, 0.0f, 0.0f};  // cells per unit length
+    float grid_off[3] = {0.0f, 0.0f, 0.0f};  // -origin * inv: the cell coordinate is fma(o, inv, off)
 };
 
 // Validate + build (host only).  Returns RT_OK or an rt_status, with `err` set.  with_texels = false computes

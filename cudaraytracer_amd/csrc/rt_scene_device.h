@@ -24,6 +24,10 @@ struct DeviceScene {
     uint32_t flat_runs[2] = {0u, 0u};  // HostScene::flat_runs
     const void* prim_source = nullptr;  // per `prims` record the index of its hittable in the caller's description
     const void* flat_source = nullptr;  // ... per prims_flat record, or NULL (rt_gbuffer's prim_id)
+    const void* leaf_records = nullptr;  // bounce entries (rt_bounce_entry.h): uint4 per leaf, or NULL = no table
+    const void* bounce_grid = nullptr;   // ... uint16 per grid cell: the index of a leaf record
+    uint32_t grid_dim[3] = {0u, 0u, 0u};
+    float grid_inv[3] = {0.0f, 0.0f, 0.0f}, grid_off[3] = {0.0f, 0.0f, 0.0f};
     const void* mats = nullptr;    // float4 × 3 per material
     const void* imgs = nullptr;    // int4 per image
     const void* texels = nullptr;  // RGB8

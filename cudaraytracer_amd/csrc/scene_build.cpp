@@ -14,6 +14,7 @@
 #include <cstring>
 #include <numeric>
 
+#include "rt_bounce_entry.h"
 #include "rt_internal.h"
 
 namespace rt {
@@ -222,6 +223,214 @@ void pack_prim(const rt_hittable_desc& h, float* o) {
         o[4] = g.b1; o[5] = 0.0f; o[6] = 0.0f;
     }
     o[7] = bits_to_float(tag);
+}
+
+// The 64-B node record (rt_internal.h).
+void pack_node16(const Builder::Node& n, float* o) {
+    o[0] = n.box[0].lo[0]; o[1] = n.box[0].hi[0]; o[2] = n.box[0].lo[1]; o[3] = n.box[0].hi[1];
+    o[4] = n.box[1].lo[0]; o[5] = n.box[1].hi[0]; o[6] = n.box[1].lo[1]; o[7] = n.box[1].hi[1];
+    o[8] = n.box[0].lo[2]; o[9] = n.box[0].hi[2]; o[10] = n.box[1].lo[2]; o[11] = n.box[1].hi[2];
+    o[12] = bits_to_float((uint32_t)n.child[0]);
+    o[13] = bits_to_float((uint32_t)n.child[1]);
+    o[14] = 0.0f;
+    o[15] = 0.0f;
+}
+
+// The 48-B node record: the three box float4 of the 64-B one.  The child references also ride in the low bytes of the
+// planes (lo_x, hi_x of each child: bits 0-15; wide: lo_y, hi_y: bits 16-31), so a lane's three 16-B box loads carry
+// them and the vector path needs no fourth load (render.hip).  Each carrier plane moves outward by < 512 ulps (lo
+// down, hi up): the box only grows, and the culling stays conservative.
+void pack_node48(const Builder::Node& n, const bool wide, float* o48) {
+    float o[16];
+    pack_node16(n, o);
+    for (int k = 0; k < 12; k++) o48[k] = o[k];
+    for (int c = 0; c < 2; c++) {
+        const uint32_t r = (uint32_t)n.child[c];
+        float* q = o48 + 4 * c;  // lo_x, hi_x, lo_y, hi_y of child c
+        q[0] = with_low_byte(q[0], r & 0xffu, false);
+        q[1] = with_low_byte(q[1], (r >> 8) & 0xffu, true);
+        if (wide) {
+            q[2] = with_low_byte(q[2], (r >> 16) & 0xffu, false);
+            q[3] = with_low_byte(q[3], r >> 24, true);
+        }
+    }
+}
+
+// Bounce entries (rt_bounce_entry.h): the chain nodes behind the real ones in nodes48 / refs, one record per leaf and
+// the origin grid.  16-bit-reference scenes whose real + chain nodes stay below 0x7fff; else no table.
+void build_bounce_entries(const Builder& B, HostScene* out) {
+    const uint32_t N = out->num_nodes;
+    if (out->wide_refs || N == 0) return;
+    struct Step { int node, side; };
+    struct Leaf { int ref; std::vector<Step> path; Box box; };
+    std::vector<Leaf> leaves;
+    std::vector<uint32_t> height(N, 0u);  // internal nodes on the longest way down from a node, itself counted
+    {
+        std::vector<Step> path;
+        std::function<uint32_t(int)> walk = [&](const int n) -> uint32_t {
+            uint32_t h = 0;
+            for (int side = 0; side < 2; side++) {
+                path.push_back(Step{n, side});
+                const int c = B.nodes[n].child[side];
+                if (c < 0) leaves.push_back(Leaf{c, path, B.nodes[n].box[side]});
+                else h = std::max(h, walk(c));
+                path.pop_back();
+            }
+            return height[n] = h + 1u;
+        };
+        walk(0);
+    }
+    const auto ref_height = [&](const int r) { return r < 0 ? 0u : height[r]; };
+    // chain node (A_2k, side of its on-path child): children S_2k (off A_2k) and S_2k-1 (off A_2k-1)
+    std::vector<Builder::Node> chain;
+    std::vector<int> chain_of((size_t)N * 2, -1);
+    std::vector<std::array<uint32_t, kTileEntryMax>> records;
+    for (const Leaf& L : leaves) {
+        const size_t a = L.path.size();
+        std::vector<int> refs;  // behind the own leaf, from the deepest up
+        const auto sibling = [&](const size_t i) { return B.nodes[L.path[i].node].child[1 - L.path[i].side]; };  // S_(i+1)
+        if (a & 1u) refs.push_back(sibling(a - 1));
+        for (size_t k = a / 2; k >= 1; k--) {
+            const Step& lo = L.path[2 * k - 1];  // A_2k
+            const Step& up = L.path[2 * k - 2];  // A_2k-1
+            int& id = chain_of[(size_t)lo.node * 2 + (size_t)lo.side];
+            if (id < 0) {
+                id = (int)(N + chain.size());
+                Builder::Node c;
+                c.child[0] = B.nodes[lo.node].child[1 - lo.side];
+                c.box[0] = B.nodes[lo.node].box[1 - lo.side];
+                c.child[1] = B.nodes[up.node].child[1 - up.side];
+                c.box[1] = B.nodes[up.node].box[1 - up.side];
+                chain.push_back(c);
+            }
+            refs.push_back(id);
+        }
+        std::array<uint32_t, kTileEntryMax> e;
+        e.fill(kTileEntryNone);
+        // The kernel's stack holds out->depth entries above its pads.  Reference j (0 = first) is visited with
+        // m - 1 - j entries below it; a visit with h entries below writes entry h, and a subtree of `height` internal
+        // levels under it reaches entry h + height - 1 (a chain node's near child is visited one entry higher).
+        const size_t m = refs.size();
+        bool fits = m <= kBounceChainMax && m >= 1 && m - 1 <= out->depth;
+        for (size_t j = 0; j < m && fits; j++) {
+            const uint32_t h = (uint32_t)(m - 1 - j);
+            uint32_t top = 0;  // the highest entry written, + 1
+            if (refs[j] >= (int)N) {
+                const Builder::Node& c = chain[(size_t)refs[j] - N];
+                top = h + 1u + std::max(ref_height(c.child[0]), ref_height(c.child[1]));
+            } else if (refs[j] >= 0) {
+                top = h + height[refs[j]];
+            }
+            fits = top <= out->depth;
+        }
+        if (fits) {
+            e[0] = (uint32_t)L.ref & 0xffffu;
+            for (size_t j = 0; j < m; j++) e[1 + j] = (uint32_t)refs[j] & 0xffffu;
+        } else {
+            e[0] = kTileEntryRoot;
+        }
+        records.push_back(e);
+    }
+    if (N + chain.size() >= 0x7fffu || records.size() > 0xffffu) return;
+
+    // The origin grid over the non-spanning primitives' boxes
+    Box scene;
+    scene.empty();
+    for (const BuildPrim& p : B.prims) scene.grow(p.box);
+    const auto spanning = [&](const BuildPrim& p) {
+        int wide_axes = 0;
+        for (int i = 0; i < 3; i++)
+            if (p.box.hi[i] - p.box.lo[i] > 0.5f * (scene.hi[i] - scene.lo[i])) wide_axes++;
+        return wide_axes >= 2;
+    };
+    Box g;
+    g.empty();
+    std::vector<char> candidate(leaves.size(), 0);  // the leaf holds a non-spanning primitive
+    bool any = false;
+    for (size_t l = 0; l < leaves.size(); l++) {
+        const uint32_t r = ~(uint32_t)leaves[l].ref, first = r >> 2, count = (r & 3u) + 1u;
+        for (uint32_t i = first; i < first + count; i++) {
+            const BuildPrim& p = B.prims[B.order[i]];
+            if (spanning(p)) continue;
+            g.grow(p.box);
+            candidate[l] = 1;
+            any = true;
+        }
+    }
+    if (!any) {  // every primitive spans: the grid covers the scene, every leaf is a candidate
+        g = scene;
+        std::fill(candidate.begin(), candidate.end(), 1);
+    }
+    float ext[3];
+    double volume = 1.0;
+    int flat_axes = 0;
+    for (int i = 0; i < 3; i++) {
+        ext[i] = g.hi[i] - g.lo[i];
+        if (!(ext[i] > 0.0f) || !std::isfinite(ext[i])) { ext[i] = 0.0f; flat_axes++; }
+        else volume *= (double)ext[i];
+    }
+    if (!std::isfinite(g.lo[0]) || !std::isfinite(g.lo[1]) || !std::isfinite(g.lo[2]) || !std::isfinite(volume)) return;
+    const double target = (double)std::min<size_t>(kBounceGridMaxCells, std::max<size_t>(1, 4 * leaves.size()));
+    double edge = flat_axes == 3 ? 1.0 : std::pow(volume / target, 1.0 / (double)(3 - flat_axes));
+    uint32_t dim[3];
+    for (;;) {
+        uint64_t cells = 1;
+        for (int i = 0; i < 3; i++) {
+            const double d = ext[i] > 0.0f && edge > 0.0 ? std::ceil((double)ext[i] / edge) : 1.0;
+            dim[i] = (uint32_t)std::min(std::max(d, 1.0), 256.0);
+            cells *= dim[i];
+        }
+        if (cells <= kBounceGridMaxCells) break;
+        edge *= 1.1;
+    }
+    for (int i = 0; i < 3; i++) {
+        out->grid_dim[i] = dim[i];
+        out->grid_origin[i] = g.lo[i];
+        out->grid_inv[i] = ext[i] > 0.0f ? (float)dim[i] / ext[i] : 0.0f;
+        if (!std::isfinite(out->grid_inv[i])) out->grid_inv[i] = 0.0f;
+        out->grid_off[i] = -(g.lo[i] * out->grid_inv[i]);
+    }
+    out->bounce_grid.resize((size_t)dim[0] * dim[1] * dim[2]);
+    for (uint32_t z = 0; z < dim[2]; z++)
+        for (uint32_t y = 0; y < dim[1]; y++)
+            for (uint32_t x = 0; x < dim[0]; x++) {
+                const uint32_t cell[3] = {x, y, z};
+                float c[3];
+                for (int i = 0; i < 3; i++)
+                    c[i] = out->grid_inv[i] > 0.0f ? g.lo[i] + ((float)cell[i] + 0.5f) / out->grid_inv[i] : g.lo[i];
+                size_t best = 0;
+                float best_area = INFINITY, best_dist = INFINITY;
+                for (size_t l = 0; l < leaves.size(); l++) {
+                    if (!candidate[l]) continue;
+                    const Box& b = leaves[l].box;
+                    float d2 = 0.0f;
+                    for (int i = 0; i < 3; i++) {
+                        const float d = std::max(std::max(b.lo[i] - c[i], c[i] - b.hi[i]), 0.0f);
+                        d2 += d * d;
+                    }
+                    const float area = b.area();
+                    // a containing box beats any other; among those the smallest, else the nearest
+                    if (d2 < best_dist || (d2 == best_dist && area < best_area)) {
+                        best = l;
+                        best_dist = d2;
+                        best_area = area;
+                    }
+                }
+                out->bounce_grid[((size_t)z * dim[1] + y) * dim[0] + x] = (uint16_t)best;
+            }
+
+    out->num_chain_nodes = (uint32_t)chain.size();
+    out->chain_nodes.resize(chain.size() * 16);
+    out->nodes48.resize((size_t)(N + chain.size()) * 12);
+    out->refs.resize((size_t)N + chain.size());
+    for (size_t i = 0; i < chain.size(); i++) {
+        pack_node16(chain[i], out->chain_nodes.data() + i * 16);
+        pack_node48(chain[i], false, out->nodes48.data() + (N + i) * 12);
+        out->refs[N + i] = ((uint32_t)chain[i].child[0] & 0xffffu) | ((uint32_t)chain[i].child[1] << 16);
+    }
+    out->leaf_records.resize(records.size() * 4);
+    for (size_t i = 0; i < records.size(); i++)
+        for (int w = 0; w < 4; w++) out->leaf_records[4 * i + w] = records[i][2 * w] | (records[i][2 * w + 1] << 16);
 }
 
 // The reference BVH over objs[b, e) exactly as the BVHNode constructor builds it (Hittable.cuh:303-385): the range is
@@ -528,40 +737,15 @@ int build_host_scene(const rt_scene_desc* desc, HostScene* out, std::string* err
     out->depth = B.max_depth;
 
     out->nodes.resize((size_t)out->num_nodes * 16);
-    for (uint32_t i = 0; i < out->num_nodes; i++) {
-        const Builder::Node& n = B.nodes[i];
-        float* o = out->nodes.data() + (size_t)i * 16;
-        o[0] = n.box[0].lo[0]; o[1] = n.box[0].hi[0]; o[2] = n.box[0].lo[1]; o[3] = n.box[0].hi[1];
-        o[4] = n.box[1].lo[0]; o[5] = n.box[1].hi[0]; o[6] = n.box[1].lo[1]; o[7] = n.box[1].hi[1];
-        o[8] = n.box[0].lo[2]; o[9] = n.box[0].hi[2]; o[10] = n.box[1].lo[2]; o[11] = n.box[1].hi[2];
-        o[12] = bits_to_float((uint32_t)n.child[0]);
-        o[13] = bits_to_float((uint32_t)n.child[1]);
-        o[14] = 0.0f;
-        o[15] = 0.0f;
-    }
     // 16-bit references (internal nodes < 0x7fff, leaves ~(first << 2 | count - 1) with first < 8192) unless the
     // tree is too large: then 32-bit ones (the kernels' WIDE builds, render.hip RefW)
     out->wide_refs = !(out->num_nodes < 0x7fffu && out->num_prims < 8192u);
     out->nodes48.resize((size_t)out->num_nodes * 12);
     out->refs.resize((size_t)out->num_nodes * (out->wide_refs ? 2 : 1));
     for (uint32_t i = 0; i < out->num_nodes; i++) {
-        float* o48 = out->nodes48.data() + (size_t)i * 12;
-        for (int k = 0; k < 12; k++) o48[k] = out->nodes[(size_t)i * 16 + k];
+        pack_node16(B.nodes[i], out->nodes.data() + (size_t)i * 16);
+        pack_node48(B.nodes[i], out->wide_refs, out->nodes48.data() + (size_t)i * 12);
         const Builder::Node& n = B.nodes[i];
-        // The child references also ride in the low bytes of the planes (lo_x, hi_x of each child: bits 0-15;
-        // wide: lo_y, hi_y: bits 16-31), so a lane's three 16-B box loads carry them and the vector path needs
-        // no fourth load (render.hip).  Each carrier plane moves outward by < 512 ulps (lo down, hi up): the box
-        // only grows, and the culling stays conservative.
-        for (int c = 0; c < 2; c++) {
-            const uint32_t r = (uint32_t)n.child[c];
-            float* q = o48 + 4 * c;  // lo_x, hi_x, lo_y, hi_y of child c
-            q[0] = with_low_byte(q[0], r & 0xffu, false);
-            q[1] = with_low_byte(q[1], (r >> 8) & 0xffu, true);
-            if (out->wide_refs) {
-                q[2] = with_low_byte(q[2], (r >> 16) & 0xffu, false);
-                q[3] = with_low_byte(q[3], r >> 24, true);
-            }
-        }
         if (out->wide_refs) {
             out->refs[2 * (size_t)i] = (uint32_t)n.child[0];
             out->refs[2 * (size_t)i + 1] = (uint32_t)n.child[1];
@@ -569,6 +753,7 @@ int build_host_scene(const rt_scene_desc* desc, HostScene* out, std::string* err
             out->refs[i] = ((uint32_t)n.child[0] & 0xffffu) | ((uint32_t)n.child[1] << 16);
         }
     }
+    build_bounce_entries(B, out);
     // (at least one record: the BVH kernels' shade() loads record 0 for a miss before it knows the ray missed, so an
     // empty scene carries one zero record that no traversal reaches)
     out->prims.assign((size_t)std::max(out->num_prims, 1u) * 8, 0.0f);

@@ -185,7 +185,9 @@ const char* rt_version(void);
  * 7: rt_gbuffer, rt_denoise, rt_denoise_scratch_bytes.  8: rt_temporal.  9: rt_scene_motion, rt_temporal_dynamic,
  * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE.  12: RT_TUNE_PATH_END_STEP.
  * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes.  14: rt_query_rays; rt_gbuffer and
- * rt_trace_rays take scenes with 32-bit BVH references. */
+ * rt_trace_rays take scenes with 32-bit BVH references; later additions that change no structure layout, counter
+ * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells
+ * (a caller asks the library for them by name). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
@@ -826,6 +828,33 @@ int rt_build_host_tables(const rt_scene_desc* desc, float* nodes, float* prims, 
 int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* inputs, uint32_t width, uint32_t height,
                          const rt_tiling* tiling, uint32_t flags, uint32_t first_tile, uint32_t num_tiles,
                          uint32_t* records);
+
+/* Bounce entries: the v3 kernels (variants 2, 3; scenes with 16-bit references) start a bounce ray at a BVH
+ * leaf near its origin instead of the root.  Behind the scene's real nodes the 48-byte node table holds "chain nodes",
+ * whose two children are two of the sibling subtrees along a leaf's ancestor path; a 16-byte record per leaf (eight
+ * 16-bit references: the leaf, then its chain from the deepest reference up, padded with 0x7fff; entry 0 = 0: start at
+ * the root) covers the whole tree; and a 3-D grid over the scene's non-spanning primitives maps a ray origin to a record.
+ * Same pixels, RNG states and ray counts whether on (default) or off.  Thread-local, like rt_set_tuning; returns the
+ * previous value, or RT_ERR_INVALID_ARGUMENT for a value other than 0 or 1. */
+int rt_set_bounce_entries(int on);
+
+/* Those tables, built on the host only (for inspection/tests).  Size query with NULL arrays: info->num_records = 0 says
+ * that the scene has no table (32-bit references, or real + chain nodes would not fit 16 bits).  chain_nodes: 16 floats
+ * per chain node in rt_build_host_tables' node layout (the boxes as they are before the references are packed into
+ * their low bytes); nodes48: 12 floats per real and chain node (the v3 kernels' table); refs: one word per real and
+ * chain node (child 0 | child 1 << 16); records: 4 words per leaf; grid: grid_dim[0] * [1] * [2] record indices, x
+ * fastest. */
+typedef struct rt_bounce_entries_info {
+    uint32_t num_nodes, num_chain_nodes, num_records, depth;
+    uint32_t grid_dim[3];
+    float grid_origin[3];
+    float grid_inv[3]; /* cells per unit length */
+    float grid_off[3]; /* -origin * inv: an origin's cell coordinate is fma(o, inv, off), clamped to the grid */
+} rt_bounce_entries_info;
+int rt_bounce_entries_host(const rt_scene_desc* desc, float* chain_nodes, float* nodes48, uint32_t* refs,
+                           uint32_t* records, uint16_t* grid, rt_bounce_entries_info* info);
+/* The grid cells of n origins (x, y, z each) as the kernel computes them. */
+int rt_bounce_entry_cells(const rt_bounce_entries_info* info, const float* origins, uint32_t n, uint32_t* cells);
 
 /* glibc random_r TYPE_3 restatement: rand() sequence after srand(seed) (RND macro, Math.cuh:12). */
 typedef struct rt_glibc_rand { int32_t r[34]; uint32_t idx; } rt_glibc_rand;

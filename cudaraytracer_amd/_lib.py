@@ -70,6 +70,8 @@ EXPORTED = [
     "rt_reference_graph_flatten",
     "rt_build_host_tables",
     "rt_tile_entries_host",
+    "rt_set_tile_occlusion",
+    "rt_tile_entries_device",
     "rt_set_bounce_entries",
     "rt_bounce_entries_host",
     "rt_bounce_entry_cells",
@@ -147,6 +149,10 @@ def _declare(lib: C.CDLL) -> None:
     if LIB_PATH == _IN_TREE or hasattr(lib, "rt_tile_entries_host"):  # (an A/B build of an older revision lacks it)
         lib.rt_tile_entries_host.argtypes = [P(abi.SceneDesc), P(abi.InputStruct), C.c_uint32, C.c_uint32, P(abi.Tiling),
                                              C.c_uint32, C.c_uint32, C.c_uint32, P(C.c_uint32)]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_set_tile_occlusion"):  # (an A/B build of an older revision lacks it)
+        lib.rt_set_tile_occlusion.argtypes = [C.c_int]
+        lib.rt_tile_entries_device.argtypes = [vp, P(abi.InputStruct), C.c_uint32, C.c_uint32, P(abi.Tiling), C.c_uint32,
+                                               vp, vp]
     if LIB_PATH == _IN_TREE or hasattr(lib, "rt_set_bounce_entries"):  # (an A/B build of an older revision lacks them)
         lib.rt_set_bounce_entries.argtypes = [C.c_int]
         lib.rt_bounce_entries_host.argtypes = [P(abi.SceneDesc), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32),

@@ -4174,6 +4174,10 @@ thread_local int g_path_end_step = 1;
 // rt_set_bounce_entries: 1 (default) = the v3 kernels start a bounce ray at a leaf near its origin (rt_bounce_entry.h;
 // scenes with the table), 0 = at the root (A/B, tests)
 thread_local int g_bounce_entries = 1;
+// rt_set_tile_occlusion: 1 (default) = the entry records leave out the candidates hidden behind a sphere that covers
+// the tile (rt_tile_entry.h tile_occlusion), 0 = they hold every primitive the beam can touch (A/B, tests); they also
+// hold every one while RT_TUNE_CAMERA_RESOLVE is at an A/B value (not 1): tile_frame_of
+thread_local int g_tile_occlusion = 1;
 
 // One row per rt_tuning_key, in the enum's order: where the value lives, the values rt_set_tuning accepts (lo..hi,
 // multiples of `step`, powers of two where `pow2`) and what it says when it refuses one.
@@ -4492,6 +4496,10 @@ TileFrame tile_frame_of(const dev::KParams& P, const bool wide_refs, const uint3
     F.num_prims = P.num_prims;
     F.wide_refs = wide_refs ? 1u : 0u;
     F.max_entries = std::min<uint32_t>(kTileEntryMax, depth + 2u);
+    // (part of EntryTable::frame: a change refills the table.)  Only with the pre-step as the product runs it: the A/B
+    // values of RT_TUNE_CAMERA_RESOLVE (0, a cap of 2..32) compare the scan and the leaf chain on the records of every
+    // touched primitive, as they did when the earlier rounds were measured with them.
+    F.occlusion = g_tile_occlusion && g_camera_resolve == 1 ? 1u : 0u;
     return F;
 }
 
@@ -4778,6 +4786,37 @@ int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* input
     return RT_OK;
 }
 
+// The same records by the pre-pass kernel itself, into the caller's device buffer (16 B per tile of the rank's rows).
+int rt_tile_entries_device(const rt_scene* scene, const rt_input_struct* inputs, uint32_t width, uint32_t height,
+                           const rt_tiling* tiling, uint32_t flags, void* records, rt_stream stream) {
+    if (!scene || !inputs || !tiling || !records) {
+        set_error("rt_tile_entries_device: NULL argument");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (!tiling_ok(*tiling) || width == 0 || height == 0) {
+        set_error("rt_tile_entries_device: invalid frame or tiling");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const DeviceScene& S = scene->dev;
+    dev::KParams P;
+    std::memset(&P, 0, sizeof(P));
+    P.num_nodes = S.num_nodes;
+    P.num_prims = S.num_prims;
+    fill_frame(P, width, height, *tiling, (flags & RT_FLAG_FAITHFUL_GRID) != 0);
+    P.tiles_x = (width + 7u) / 8u;
+    fill_camera(P, *inputs, width, height);
+    const uint64_t tiles = (uint64_t)P.tiles_x * ((tiling->local_rows + 7u) / 8u);
+    if (tiles == 0 || tiles > 0x7fffffffull) {
+        set_error("rt_tile_entries_device: tile count out of range");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const TileFrame F = tile_frame_of(P, S.wide_refs, S.depth);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(dev::tile_entries_kernel, dim3(((uint32_t)tiles + 63u) / 64u), dim3(64), 0, (hipStream_t)stream,
+                       (const float*)S.nodes, (const float*)S.prims, F, (TileRecord*)records, (uint32_t)tiles);
+    return hip_check(hipGetLastError(), "rt_tile_entries_device: kernel launch", RT_ERR_LAUNCH);
+}
+
 // rt_trace_rays' automatic rays per lane: enough waves to fill the device (8 per SIMD), at most 16 rays per lane
 static uint32_t auto_rays_per_lane(const uint32_t n) {
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, (uint64_t)n / (64ull * 8192ull)));
@@ -4939,6 +4978,16 @@ int rt_set_bounce_entries(int on) {
     }
     const int prev = g_bounce_entries;
     g_bounce_entries = on;
+    return prev;
+}
+
+int rt_set_tile_occlusion(int on) {
+    if (on != 0 && on != 1) {
+        set_error("rt_set_tile_occlusion: the value must be 0 or 1");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const int prev = g_tile_occlusion;
+    g_tile_occlusion = on;
     return prev;
 }
 

@@ -17,6 +17,8 @@
 // every leaf whose padded box meets the beam, each run of consecutive primitives that can meet it themselves (a sphere
 // by its centre and radius, a rectangle by its extents) — a part of a leaf is walked like a leaf.  They come in
 // traversal order, padded with the sentinel 0x7fff — entry 0 = 0x7fff: no candidate at all, the tile's camera rays miss.
+// With TileFrame::occlusion the candidates that lie behind a sphere every ray of the beam hits are left out
+// (tile_occlusion below): a tile inside a sphere's silhouette does not test the ground and the spheres behind it.
 //
 // The classifier is one host + device function, so that the pre-pass kernel and rt_tile_entries_host agree.
 #pragma once
@@ -53,6 +55,7 @@ struct TileFrame {
     uint32_t num_nodes, num_prims;
     uint32_t wide_refs;    // the scene's references need 32 bits: they do not fit the record
     uint32_t max_entries;  // at most kTileEntryMax; max_entries − 2 ≤ the kernel's stack entries
+    uint32_t occlusion;    // drop candidates hidden behind a covering sphere (tile_occlusion, rt_set_tile_occlusion)
 };
 
 RT_TILE_HD inline TileRecord tile_record_root() {
@@ -61,6 +64,151 @@ RT_TILE_HD inline TileRecord tile_record_root() {
 }
 
 RT_TILE_HD inline bool tile_finite(const float v) { return v - v == 0.0f; }
+
+// Number of maximal runs of set bits in a run's 4-bit keep mask (its references), and the mask with the gap behind its
+// first kept part filled (for a mask of two or more parts).
+RT_TILE_HD inline uint32_t tile_mask_runs(const uint32_t m) {
+    const uint32_t s = m & ~(m << 1);
+    return (s & 1u) + (s >> 1 & 1u) + (s >> 2 & 1u) + (s >> 3 & 1u);
+}
+RT_TILE_HD inline uint32_t tile_mask_close_gap(uint32_t m) {
+    uint32_t j = 0;
+    while (j < 4u && !(m >> j & 1u)) j++;
+    while (j < 4u && (m >> j & 1u)) j++;
+    while (j < 4u && !(m >> j & 1u)) m |= 1u << j++;
+    return m;
+}
+
+// A sphere record as the beam's apex E sees it (binary64): distance d of its centre, the cosine and sine of the angle θ
+// between the centre's direction and the cone's axis, |radius|, and the shrunk and grown radii r_s < r < r_g that
+// stand for Sphere::Hit's rounding (tile_occlusion).  False: a value is not finite, or d or the radius is 0 — such a
+// sphere is left alone.
+struct TileSphereView {
+    double d, cos_t, sin_t, r, r_s, r_g, mag;
+};
+RT_TILE_HD inline bool tile_sphere_view(const float* p, const double E[3], const double axis[3], const double e_mag,
+                                        const double s_far, TileSphereView& s) {
+    if (!tile_finite(p[0]) || !tile_finite(p[1]) || !tile_finite(p[2]) || !tile_finite(p[3])) return false;
+    const double v[3] = {(double)p[0] - E[0], (double)p[1] - E[1], (double)p[2] - E[2]};
+    s.r = p[3] < 0.0f ? -(double)p[3] : (double)p[3];
+    s.d = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+    if (!(s.d > 0.0) || !(s.r > 0.0)) return false;
+    s.cos_t = (v[0] * axis[0] + v[1] * axis[1] + v[2] * axis[2]) / s.d;
+    const double s2 = 1.0 - s.cos_t * s.cos_t;
+    s.sin_t = s2 > 0.0 ? sqrt(s2) : 0.0;
+    const double c1 = (p[0] < 0.0f ? -(double)p[0] : (double)p[0]) + (p[1] < 0.0f ? -(double)p[1] : (double)p[1]) +
+                      (p[2] < 0.0f ? -(double)p[2] : (double)p[2]);
+    s.mag = e_mag + c1 + s.r + s_far;
+    const double eps = 0x1p-18 * (s.mag * s.mag) / s.r;
+    s.r_s = s.r - (0x1p-10 * s.r + eps);
+    s.r_g = s.r + (0x1p-16 * s.r + eps);
+    return s.r_g - s.r_g == 0.0;
+}
+
+// Occlusion culling of a tile's candidates (F.occlusion): clears in run_keep the primitives that lie, for every camera
+// ray of the tile, behind a sphere that every camera ray of the tile hits.  In binary64 from the classifier's own E and
+// corner directions, with + − × ÷ and sqrt alone, so host and device agree bit for bit.
+//
+// The beam lies in the circular cone about the axis a = Dc/|Dc| with half angle ρ, cos ρ = the smallest a·D_k/|D_k| of
+// the four corners (a circular cone is convex, so it holds the parallelogram the corners span), 1 − cos ρ grown by
+// 2^-8 of itself.  A ray of the beam at angle φ to the direction of a sphere's centre (distance d from E, radius r)
+// enters the sphere at distance f(φ) = d cos φ − sqrt(r² − d² sin² φ) from E, which grows with φ where d > r; over the
+// cone φ ranges within [max(0, θ − ρ), θ + ρ].
+//
+// Sphere::Hit in binary32 (v3_resolve_camera, the leaf loop) computes disc = b² − a·c from oc = o − centre with
+// |oc| ≤ M = |E|₁ + |centre|₁ + r + s_far (s_far = −s_e·max|D_k|, the farthest ray start from E): b is off by at most
+// 2^-22·M and disc by at most 2^-20·M² (three-term dot products of operands below M, the record's r² rounded once,
+// a = |rd|² within 2^-22 of 1).  So the disc it sees is the exact one of a sphere of the same centre with a radius
+// between r_s = r − (2^-10·r + eps) and r_g = r + (2^-16·r + eps), eps = 2^-18·M²/r: r_g² − r² and r² − r_s² are at
+// least 2^-17·M², eight times the bound.  eps, not the relative term, is what dominates Sphere::Hit's error — for a
+// sphere of radius 0.2 seen from 10 units in a scene of M = 25 it is 6 % of r, where 2^-10·r alone would be below the
+// error of disc.  The relative terms stand above the rounding of the record's r and r²: 2^-10 on the occluder, whose
+// shrinking only costs the tiles on its rim, 2^-16 (the classifier's own, prim_meets) on a primitive to be dropped —
+// 2^-10 there would raise a ground sphere of radius 1000 by a whole unit and keep it in every tile.  The square root
+// being monotonic, the near root Sphere::Hit computes lies between the exact entry distances of the grown and of the
+// shrunk sphere, give or take b's 2^-22·M and the correctly rounded square root and division (2^-21·M together).  The rays' own rounding — a start within 2^-22·M of
+// its place on the half line through E, a direction within 2^-23 — moves a centre by less than 2^-18·M ≤ eps as the
+// ray sees it, and in angle by three orders of magnitude less than the pixel the beam is padded with (header).
+//
+// A (a sphere) covers the tile when r_s > 0, θ < 90°, cos(θ + ρ) > sqrt(1 − (r_s/d)²) — the cone lies inside the shrunk
+// sphere's silhouette, so every ray has disc > 0 in binary32 too — and d − r_g > s_far + 16·kTmin + 2^-10·M: the entry
+// root of every ray is above kTmin and is accepted.  Then every camera ray of the tile records a hit at or before
+// T_A = f_{r_s}(θ + ρ) (+ 2^-21·M) from E.  B (a sphere) can only be entered at or after L_B = f_{r_g}(max(0, θ_B − ρ))
+// (− 2^-21·M_B), and both of its roots lie there.  B is dropped where L_B > T_A·(1 + 2^-10) + 2^-18·(M_A + M_B) for
+// the smallest T_A of the tile: along every ray A's accepted t is strictly below any t B could report (the same ray
+// start is subtracted from both), so B never is the closest hit, never ties with it (kTieBit is set for a tie at the
+// closest hit so far and is overwritten by a strictly closer acceptance — A's), and the hit record the scan or the leaf
+// chain ends with — primitive, tag, t_best, tie bit — is the one it ends with when B is tested.  A itself is never
+// dropped (L_A ≤ T_A).  Rectangles, unknown types and anything non-finite stay candidates and never occlude.
+RT_TILE_HD inline void tile_occlusion(const float* prims, const float* E, const float (*D)[3], const float* Dc,
+                                      const float s_e, const uint32_t* run_first, const uint32_t* run_count,
+                                      uint32_t* run_keep, const uint32_t n_e) {
+    if (n_e == 1 && run_count[0] == 1) return;
+    const double Ed[3] = {(double)E[0], (double)E[1], (double)E[2]};
+    double axis[3] = {(double)Dc[0], (double)Dc[1], (double)Dc[2]};
+    const double alen = sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (!(alen > 0.0) || alen - alen != 0.0) return;
+    for (int a = 0; a < 3; a++) axis[a] /= alen;
+    double cos_rho = 1.0, dlen_max = 0.0;
+    for (int k = 0; k < 4; k++) {
+        const double x = D[k][0], y = D[k][1], z = D[k][2];
+        const double len = sqrt(x * x + y * y + z * z);
+        if (!(len > 0.0)) return;
+        const double c = (x * axis[0] + y * axis[1] + z * axis[2]) / len;
+        if (!(c <= 1.0)) return;  // (a NaN; c can only exceed 1 by rounding, which the slack below covers)
+        if (c < cos_rho) cos_rho = c;
+        if (len > dlen_max) dlen_max = len;
+    }
+    cos_rho = 1.0 - ((1.0 - cos_rho) * (1.0 + 0x1p-8) + 0x1p-44);
+    if (!(cos_rho > 0.5)) return;
+    const double sin_rho = sqrt(1.0 - cos_rho * cos_rho);
+    const double s_far = -(double)s_e * dlen_max;
+    const double e_mag = (Ed[0] < 0.0 ? -Ed[0] : Ed[0]) + (Ed[1] < 0.0 ? -Ed[1] : Ed[1]) + (Ed[2] < 0.0 ? -Ed[2] : Ed[2]);
+    if (!(s_far >= 0.0) || s_far - s_far != 0.0 || e_mag - e_mag != 0.0) return;
+    // per candidate L_B and M_B (L_B < 0: stays whatever covers the tile), and the covering sphere with the smallest T_A
+    double lower[kTileEntryMax * 4], mags[kTileEntryMax * 4];
+    double t_min = 0.0, mag_min = 0.0;
+    uint32_t a_k = kTileEntryMax * 4, k = 0;
+    for (uint32_t i = 0; i < n_e; i++)
+        for (uint32_t j = 0; j < run_count[i]; j++, k++) {
+            lower[k] = -1.0;
+            mags[k] = 0.0;
+            const float* p = prims + (size_t)(run_first[i] + j) * 8;
+            uint32_t tag;
+            __builtin_memcpy(&tag, p + 7, 4);
+            TileSphereView s;
+            if ((tag & 15u) != RT_SPHERE || !tile_sphere_view(p, Ed, axis, e_mag, s_far, s)) continue;
+            const double rs = s.r_s, rg = s.r_g, dd = s.d * s.d, cc = s.cos_t * cos_rho, ss = s.sin_t * sin_rho;
+            if (s.d > rg) {
+                const double c = s.cos_t >= cos_rho ? 1.0 : cc + ss;  // cos(max(0, θ − ρ))
+                const double s2 = 1.0 - c * c;
+                const double q = rg * rg - dd * (s2 > 0.0 ? s2 : 0.0);
+                // (q < 0: the cone passes the grown sphere by — it stays, as the classifier left it)
+                if (q >= 0.0) {
+                    lower[k] = s.d * c - sqrt(q);
+                    mags[k] = s.mag;
+                }
+            }
+            if (!(rs > 0.0) || !(s.cos_t > 0.0)) continue;
+            if (!(s.d - rg > s_far + 0.016 + 0x1p-10 * s.mag)) continue;
+            const double c = cc - ss;  // cos(θ + ρ), θ + ρ < 150°
+            if (!(c > 0.0)) continue;
+            const double q = rs * rs - dd * (1.0 - c * c);
+            if (!(q > 0.0)) continue;
+            const double T = s.d * c - sqrt(q);
+            if (T - T != 0.0) continue;
+            if (a_k == kTileEntryMax * 4 || T < t_min) {
+                t_min = T;
+                mag_min = s.mag;
+                a_k = k;
+            }
+        }
+    if (a_k == kTileEntryMax * 4) return;
+    k = 0;
+    for (uint32_t i = 0; i < n_e; i++)
+        for (uint32_t j = 0; j < run_count[i]; j++, k++)
+            if (k != a_k && lower[k] > t_min * (1.0 + 0x1p-10) + 0x1p-18 * (mag_min + mags[k])) run_keep[i] &= ~(1u << j);
+}
 
 // The record of tile `tile` (row-major in tiles_x) of the frame F over the 64-B node table `nodes` (rt_internal.h:
 // per node the two children's boxes and their references as int32) and the 32-B primitive records `prims`.
@@ -157,8 +305,8 @@ RT_TILE_HD inline TileRecord tile_record(const float* nodes, const float* prims,
         if (type == RT_YZRECT) return meets(k0, k1, p[1], p[2], p[3], p[4]);
         return true;  // (an unknown type stays a candidate)
     };
-    uint32_t e[kTileEntryMax];
-    for (uint32_t i = 0; i < kTileEntryMax; i++) e[i] = kTileEntryNone;
+    // the runs as they are found: first primitive, count (1 … 4) and, after tile_occlusion, which of them stay
+    uint32_t run_first[kTileEntryMax], run_count[kTileEntryMax], run_keep[kTileEntryMax];
     uint32_t n_e = 0, sp = 0;
     int32_t stack[kTileEntryStack];
     int32_t node = 0;
@@ -185,7 +333,9 @@ RT_TILE_HD inline TileRecord tile_record(const float* nodes, const float* prims,
                     }
                     if (run) {
                         if (n_e == F.max_entries) return root;
-                        e[n_e++] = ~(((first + j - run) << 2) | (run - 1u)) & 0xffffu;
+                        run_first[n_e] = first + j - run;
+                        run_count[n_e] = run;
+                        run_keep[n_e++] = (1u << run) - 1u;
                         run = 0;
                     }
                 }
@@ -201,6 +351,34 @@ RT_TILE_HD inline TileRecord tile_record(const float* nodes, const float* prims,
             next = stack[--sp];
         }
         node = next;
+    }
+    if (F.occlusion && n_e) tile_occlusion(prims, E, D, Dc, s_e, run_first, run_count, run_keep, n_e);
+    // the kept primitives, run by run: a primitive dropped from the middle of a run splits it in two references.  The
+    // record never holds more references than the n_e it holds without tile_occlusion (≤ F.max_entries): while it
+    // would, a gap between two kept parts of a run is closed by putting its primitives back.
+    uint32_t refs = 0;
+    for (uint32_t i = 0; i < n_e; i++) refs += tile_mask_runs(run_keep[i]);
+    for (uint32_t i = 0; i < n_e && refs > n_e; i++)
+        while (refs > n_e && tile_mask_runs(run_keep[i]) > 1u) {
+            run_keep[i] = tile_mask_close_gap(run_keep[i]);
+            refs--;
+        }
+    uint32_t e[kTileEntryMax];
+    for (uint32_t i = 0; i < kTileEntryMax; i++) e[i] = kTileEntryNone;
+    uint32_t n_out = 0;
+    for (uint32_t i = 0; i < n_e; i++) {
+        uint32_t run = 0;
+        for (uint32_t j = 0; j <= run_count[i]; j++) {
+            if (j < run_count[i] && (run_keep[i] >> j & 1u)) {
+                run++;
+                continue;
+            }
+            if (run) {
+                if (n_out == kTileEntryMax) return root;  // (cannot happen: refs ≤ n_e)
+                e[n_out++] = ~(((run_first[i] + j - run) << 2) | (run - 1u)) & 0xffffu;
+                run = 0;
+            }
+        }
     }
     return TileRecord{{e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16)}};
 }

@@ -100,6 +100,15 @@ class DeviceScene:
             pass
 
 
+def set_tile_occlusion(on: bool) -> bool:
+    """rt_set_tile_occlusion for the calling thread: whether the v3 kernels' tile entry records leave out candidates
+    hidden behind a covering sphere (default on; same pixels either way).  Returns the previous setting."""
+    prev = lib().rt_set_tile_occlusion(1 if on else 0)
+    if prev < 0:
+        check(prev, "rt_set_tile_occlusion")
+    return bool(prev)
+
+
 def band_rows_of(height: int, band_rows: int, num_ranks: int, rank: int) -> list[int]:
     """Global rows owned by `rank` under block-cyclic row bands (rt_tiling, include/rt_hip.h)."""
     rows = []

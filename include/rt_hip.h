@@ -186,8 +186,8 @@ const char* rt_version(void);
  * rt_scene_edit.  10: rt_tile_entries_host.  11: RT_TUNE_CAMERA_RESOLVE.  12: RT_TUNE_PATH_END_STEP.
  * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes.  14: rt_query_rays; rt_gbuffer and
  * rt_trace_rays take scenes with 32-bit BVH references; later additions that change no structure layout, counter
- * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells
- * (a caller asks the library for them by name). */
+ * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells,
+ * rt_set_tile_occlusion, rt_tile_entries_device (a caller asks the library for them by name). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
@@ -828,6 +828,20 @@ int rt_build_host_tables(const rt_scene_desc* desc, float* nodes, float* prims, 
 int rt_tile_entries_host(const rt_scene_desc* desc, const rt_input_struct* inputs, uint32_t width, uint32_t height,
                          const rt_tiling* tiling, uint32_t flags, uint32_t first_tile, uint32_t num_tiles,
                          uint32_t* records);
+
+/* Tile occlusion: the entry records leave out a primitive that lies, for every camera ray of its tile, behind a sphere
+ * that every camera ray of the tile hits (a tile inside a sphere's silhouette no longer tests the ground and the
+ * spheres behind it).  Same pixels, RNG states and ray counts whether on (default) or off; fewer primitive tests.
+ * Part of what the table is filled for: a change refills it, and rt_tile_entries_host honours it.  Applied while
+ * RT_TUNE_CAMERA_RESOLVE has its default 1; its A/B values (0, a cap of 2..32) keep the records of every primitive.  Thread-local, like
+ * rt_set_tuning; returns the previous value, or RT_ERR_INVALID_ARGUMENT for a value other than 0 or 1. */
+int rt_set_tile_occlusion(int on);
+
+/* The records of every tile of the rank's local rows as the device pre-pass writes them (the kernel rt_render launches
+ * when its table is stale), into `records`: device memory of 16 bytes per tile, ceil(width / 8) * ceil(local_rows / 8)
+ * tiles.  Enqueued on `stream`; for inspection/tests (bit-equal to rt_tile_entries_host). */
+int rt_tile_entries_device(const rt_scene* scene, const rt_input_struct* inputs, uint32_t width, uint32_t height,
+                           const rt_tiling* tiling, uint32_t flags, void* records, rt_stream stream);
 
 /* Bounce entries: the v3 kernels (variants 2, 3; scenes with 16-bit references) start a bounce ray at a BVH
  * leaf near its origin instead of the root.  Behind the scene's real nodes the 48-byte node table holds "chain nodes",

@@ -47,6 +47,7 @@ EXPORTED = [
     "rt_set_ray_dump",
     "rt_trace_rays",
     "rt_query_rays",
+    "rt_occluded_rays",
     "rt_gbuffer",
     "rt_denoise",
     "rt_denoise_scratch_bytes",
@@ -117,6 +118,8 @@ def _declare(lib: C.CDLL) -> None:
     lib.rt_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     if LIB_PATH == _IN_TREE or hasattr(lib, "rt_query_rays"):  # (an A/B build of an older revision lacks it)
         lib.rt_query_rays.argtypes = [vp, P(abi.QueryArgs), vp]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_occluded_rays"):  # (likewise)
+        lib.rt_occluded_rays.argtypes = [vp, P(abi.OcclusionArgs), vp]
     lib.rt_gbuffer.argtypes = [vp, P(abi.GBufferArgs), vp]
     lib.rt_denoise.argtypes = [P(abi.DenoiseArgs), vp]
     lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]

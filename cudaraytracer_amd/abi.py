@@ -29,7 +29,8 @@ RT_TEMPORAL_RESET = 1 << 1
 # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host;
 # 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP; 13: rt_temporal_moments, rt_denoise_variance,
 # rt_denoise_variance_scratch_bytes; 14: rt_query_rays, 32-bit references in rt_gbuffer and rt_trace_rays
-# (rt_set_bounce_entries, rt_bounce_entries_host and rt_bounce_entry_cells were added without a new number: no layout changed)
+# (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells and rt_occluded_rays were added without a new
+# number: no layout changed)
 ABI_VERSION = 14
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
@@ -204,6 +205,20 @@ class QueryArgs(C.Structure):  # rt_query_args
         ("rays_per_lane", C.c_uint32),
         ("flags", C.c_uint32),
         ("reserved", C.c_uint32),
+    ]
+
+
+class OcclusionArgs(C.Structure):  # rt_occlusion_args
+    _fields_ = [
+        ("rays", C.c_void_p),
+        ("occluded", C.c_void_p),
+        ("blocker", C.c_void_p),
+        ("counters", C.c_void_p),
+        ("n", C.c_uint32),
+        ("rays_per_lane", C.c_uint32),
+        ("count_tests", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
     ]
 
 

@@ -2060,6 +2060,7 @@ template <class T> using Lds = __attribute__((address_space(3))) T;
 // v_min/v_max(3)_f32 as plain instructions: the operands are finite FMA results or canonical values
 __device__ __forceinline__ float vmax(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "s"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmin(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float vmaxv(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ float vmax3(float a, float b, float c) { float r; asm("v_max3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 __device__ __forceinline__ float vmin3(float a, float b, float c) { float r; asm("v_min3_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c)); return r; }
 constexpr uint32_t kPrimStep = 32u;  // leaf cursor unit: bytes of one 32-B primitive record
@@ -2067,12 +2068,18 @@ constexpr uint32_t kPrimStep = 32u;  // leaf cursor unit: bytes of one 32-B prim
 // Traversal phase of one lane (v3/v4): resumes the cursor and runs the speculative while-while loop
 // until this lane's closest hit is found (mode -> MODE_SHADE) or fewer than `threshold` lanes are
 // still tracing (the wave then shades the finished lanes and regenerates them).
-template <bool COUNT_TESTS, int NODES, uint32_t STK_OFF, bool WIDE, bool EXACT = RT_BVH_EXACT != 0>
+// ANYHIT (rt_occluded_rays): the ray's range is (ray_tmin, c.t_best) — a lower end per lane where the closest-hit builds
+// have the constant kTmin, an upper end that is never written — and the first primitive whose test accepts ends the
+// lane's traversal with c.hit = its index.  No tie machinery (EXACT must be off).  The range never shrinks, so the
+// nodes a lane visits and the primitives it tests, in their order, depend on its ray alone.
+template <bool COUNT_TESTS, int NODES, uint32_t STK_OFF, bool WIDE, bool EXACT = RT_BVH_EXACT != 0, bool ANYHIT = false>
 __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
                                             const float4* __restrict__ nodes_tab, const uint32_t* __restrict__ refs,
                                             const float4* __restrict__ prims, typename RefW<WIDE>::Entry* const stk,
                                             const uint32_t threshold, const f3 ro, const f3 rd, Cursor& c,
-                                            Counts& cnt, const uint32_t ntrav = 64, const uint32_t leaf_break = 0) {
+                                            Counts& cnt, const uint32_t ntrav = 64, const uint32_t leaf_break = 0,
+                                            const float ray_tmin = kTmin) {
+    static_assert(!(ANYHIT && EXACT), "the any-hit traversal has no tie machinery");
     // node / leaf references as unsigned values of the reference width (RefW): internal nodes < kSentinel, leaf
     // references (negative in the layout) >= kLeaf; leaf == 0: no postponed leaf
     using RW = RefW<WIDE>;
@@ -2102,7 +2109,8 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
     const __amdgpu_buffer_rsrc_t rsrc_nodes_idx =
         __builtin_amdgcn_make_buffer_rsrc((void*)nodes_tab, (short)48, 0x7fffffff, 0x00020000);
     constexpr uint32_t stk_off = STK_OFF / sizeof(Entry);  // in entries
-    const float tmin_s = kTmin;  // an SGPR operand of the slab test's v_max
+    const float tmin_s = kTmin;  // an SGPR operand of the slab test's v_max (ANYHIT: ray_tmin, a VGPR one)
+    const float tmin_p = ANYHIT ? ray_tmin : kTmin;  // the primitive tests' lower end
     const __amdgpu_buffer_rsrc_t prsrc = __builtin_amdgcn_make_buffer_rsrc((void*)prims, (short)0, 0x7fffffff, 0x00020000);
     bool seen_div = false;  // COUNT_TESTS: this call has had a node iteration whose lanes held different nodes
     // Every node iteration of this call so far had all its lanes on one node (the 48-B tables' scalar path).  A
@@ -2155,10 +2163,21 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
                 // the plane distances are FMA results and t_best_c is canonical, so min/max need no
                 // canonicalising v_max (LLVM re-emits one per visit for a value carried into the loop:
                 // C2 −1.8 %)
-                c0min = vmax3(nx0, ny0, vmax(tmin_s, nz0));
-                c0max = vmin3(fx0, fy0, vmin(fz0, t_best_c)) * kSlabSlack;
-                c1min = vmax3(nx1, ny1, vmax(tmin_s, nz1));
-                c1max = vmin3(fx1, fy1, vmin(fz1, t_best_c)) * kSlabSlack;
+                if constexpr (ANYHIT) {
+                    // the far side widened by 2^-20 of its magnitude: for a far side >= 0 the very float the product
+                    // below gives (one rounding of x + x * 2^-20 either way), and still outward where a range that
+                    // reaches below 0 makes it negative
+                    const float f0 = vmin3(fx0, fy0, vmin(fz0, t_best_c)), f1 = vmin3(fx1, fy1, vmin(fz1, t_best_c));
+                    c0min = vmax3(nx0, ny0, vmaxv(ray_tmin, nz0));
+                    c0max = __builtin_fmaf(__builtin_fabsf(f0), kSlabSlack - 1.0f, f0);
+                    c1min = vmax3(nx1, ny1, vmaxv(ray_tmin, nz1));
+                    c1max = __builtin_fmaf(__builtin_fabsf(f1), kSlabSlack - 1.0f, f1);
+                } else {
+                    c0min = vmax3(nx0, ny0, vmax(tmin_s, nz0));
+                    c0max = vmin3(fx0, fy0, vmin(fz0, t_best_c)) * kSlabSlack;
+                    c1min = vmax3(nx1, ny1, vmax(tmin_s, nz1));
+                    c1max = vmin3(fx1, fy1, vmin(fz1, t_best_c)) * kSlabSlack;
+                }
             };
             if constexpr (NODES == NODES_64) {  // 64-B node: f32 boxes + two int32 references
                 const uint32_t noff = (uint32_t)node << 6;
@@ -2343,15 +2362,15 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
                     if (disc > 0) {
                         const float sq = sqrt_fast(disc);
                         float t = fast_div ? div_rn(-b - sq, a_dd, inv_a) : (-b - sq) / a_dd;
-                        if (t < t_best && t > kTmin) {
-                            t_best = t;
+                        if (t < t_best && t > tmin_p) {
+                            if (!ANYHIT) t_best = t;
                             hit = (int)i;
                             tag = __float_as_uint(p1.w);
                         } else {
                             const bool tied = EXACT && t == t_best;  // (bvh_clear: a tie at the closest hit so far)
                             t = fast_div ? div_rn(-b + sq, a_dd, inv_a) : (-b + sq) / a_dd;
-                            if (t < t_best && t > kTmin) {
-                                t_best = t;
+                            if (t < t_best && t > tmin_p) {
+                                if (!ANYHIT) t_best = t;
                                 hit = (int)i;
                                 tag = __float_as_uint(p1.w);
                             } else if (EXACT && (tied || t == t_best)) {
@@ -2363,17 +2382,24 @@ __device__ __forceinline__ void v3_traverse(const __amdgpu_buffer_rsrc_t nrsrc,
                     const float ok = type == RT_XYRECT ? ro.z : (type == RT_XZRECT ? ro.y : ro.x);
                     const float dk = type == RT_XYRECT ? rd.z : (type == RT_XZRECT ? rd.y : rd.x);
                     const float t = (p0.x - ok) * rcp_ieee(dk);
-                    if (!(t < kTmin || t > t_best)) {
+                    if (!(t < tmin_p || t > t_best)) {
                         const float oa = type == RT_YZRECT ? ro.y : ro.x, da = type == RT_YZRECT ? rd.y : rd.x;
                         const float ob = type == RT_XYRECT ? ro.y : ro.z, db = type == RT_XYRECT ? rd.y : rd.z;
                         const float xx = oa + t * da;
                         const float yy = ob + t * db;
                         if (!(xx < p0.y || xx > p0.z || yy < p0.w || yy > p1.x)) {
                             hit = EXACT && t == t_best ? (int)i | kTieBit : (int)i;  // (a rectangle re-accepts an equal t)
-                            t_best = t;
+                            if (!ANYHIT) t_best = t;
                             tag = __float_as_uint(p1.w);
                         }
                     }
+                }
+            }
+            if constexpr (ANYHIT) {
+                if (hit >= 0) {  // the first accepted primitive ends this lane's traversal (cur = end: it leaves the loop)
+                    node = RW::kSentinel;
+                    leaf = 0;
+                    break;
                 }
             }
             cur += kPrimStep;
@@ -4022,6 +4048,84 @@ __global__ __launch_bounds__(64, 4) void query_rays_kernel(const QueryParams Q) 
     }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Any-hit visibility queries with a range per ray (rt_occluded_rays): query_rays_kernel's schedule with v3_traverse's
+// ANYHIT mode.  rays[2i] = (origin, tmin), rays[2i + 1] = (direction, tmax); a ray with !(tmin <= tmax) goes to its
+// store without a traversal (and is not counted as a ray).  A lane writes its ray's byte / index itself, so the result
+// does not depend on the schedule; and since the range never shrinks, neither does the primitive that ends a traversal.
+// ---------------------------------------------------------------------------------------------------
+struct OcclusionParams {
+    KParams K;
+    const float4* rays;
+    uint8_t* occluded;
+    int32_t* blocker;
+    const int32_t* source;  // as GBufParams.source
+    uint32_t n, per_wave;
+};
+
+template <bool COUNT_TESTS, bool WIDE>
+__global__ __launch_bounds__(64, 4) void occlusion_rays_kernel(const OcclusionParams Q) {
+    using Entry = typename RefW<WIDE>::Entry;
+    const KParams* P = &Q.K;
+    extern __shared__ float4 lds[];
+    const uint32_t lane = threadIdx.x & 63u;
+    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
+    const __amdgpu_buffer_rsrc_t nrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+    stk[0] = (Entry)RefW<WIDE>::kSentinel;
+    stk[64] = (Entry)RefW<WIDE>::kSentinel;
+    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
+    const uint32_t count = min(Q.n - base, Q.per_wave);  // rays of this wave's range (base + per_wave may wrap)
+    Counts cnt{0, 0, 0, 0, 0, 0, 0};
+    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+    uint32_t ray = base + lane, nrays = 0u;
+    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro;
+    float tmin = 0.0f;
+    const auto start = [&](uint32_t i) {
+        const float4 o = Q.rays[2 * (size_t)i], d = Q.rays[2 * (size_t)i + 1];
+        ro = xyz(o);
+        rd = xyz(d);
+        tmin = o.w;
+        if (tmin <= d.w) {  // (false with a NaN at either end)
+            v3_start_trace<WIDE>(P->num_nodes, c, nrays);
+            c.t_best = d.w;  // the range's upper end: read by the traversal, never written
+        } else {
+            c.hit = -1;
+            c.mode = MODE_SHADE;
+        }
+    };
+    if (lane < count) start(ray);
+    uint32_t taken = 64u;  // wave-uniform: rays of the wave's range handed out so far
+    while (__ballot(c.mode != MODE_DONE) != 0) {
+        if (c.mode == MODE_TRAV) {
+            uint32_t thr = P->regen_threshold;
+            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false, true>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c,
+                                                                     cnt, 64u, P->leaf_break, tmin);
+        }
+        if (c.mode == MODE_SHADE) {
+            if (Q.occluded) Q.occluded[ray] = c.hit >= 0 ? (uint8_t)1 : (uint8_t)0;  // (a byte store)
+            if (Q.blocker) Q.blocker[ray] = c.hit >= 0 ? Q.source[c.hit] : -1;
+            c.mode = MODE_NEED;
+        }
+        const uint64_t needm = __ballot(c.mode == MODE_NEED);
+        if (needm != 0) {
+            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
+            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
+            if (c.mode == MODE_NEED) {
+                if (k < count) {
+                    ray = base + k;
+                    start(ray);
+                } else {
+                    c.mode = MODE_DONE;
+                }
+            }
+        }
+    }
+    cnt.rays = nrays;
+    flush_counts<COUNT_TESTS>(*P, cnt);
+}
+
 __global__ __launch_bounds__(kBlock) void render_init_kernel(uint32_t* state, uint32_t width, uint32_t local_rows,
                                                               uint32_t band_rows, uint32_t num_ranks, uint32_t rank,
                                                               unsigned long long seed_base, uint32_t soa) {  // soa: plane size
@@ -4940,6 +5044,55 @@ int rt_query_rays(const rt_scene* scene, const rt_query_args* a, rt_stream strea
     else
         hipLaunchKernelGGL(dev::query_rays_kernel<false>, dim3(grid), dim3(64), lds, s, Q);
     return hip_check(hipGetLastError(), "rt_query_rays: kernel launch", RT_ERR_LAUNCH);
+}
+
+int rt_occluded_rays(const rt_scene* scene, const rt_occlusion_args* a, rt_stream stream) {
+    // (every argument check runs before the first device call and before the scene is read)
+    const auto bad = [](const char* what) {
+        set_error(std::string("rt_occluded_rays: ") + what);
+        return RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!a) return bad("NULL args");
+    if (a->flags != 0 || a->reserved[0] != 0 || a->reserved[1] != 0) return bad("flags and reserved must be 0");
+    if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
+    if (a->count_tests > 1u) return bad("count_tests must be 0 or 1");
+    if (a->count_tests && !a->counters) return bad("count_tests without counters");
+    if (!a->occluded && !a->blocker) return bad("no output buffer");
+    const uint64_t n = a->n;
+    if (n == 0) return RT_OK;  // nothing to trace
+    if (!a->rays) return bad("NULL rays");
+    const void* const outs[3] = {a->occluded, a->blocker, a->counters};
+    const uint64_t out_bytes[3] = {n, n * 4u, (uint64_t)RT_COUNTERS_WORDS * 8u};
+    for (int o = 0; o < 3; o++) {
+        if (overlaps(outs[o], out_bytes[o], a->rays, n * 32u)) return bad("an output overlaps rays");
+        for (int p = 0; p < o; p++)
+            if (overlaps(outs[o], out_bytes[o], outs[p], out_bytes[p])) return bad("outputs overlap each other");
+    }
+    if (!scene) return bad("NULL scene");
+    const DeviceScene& S = scene->dev;
+    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
+    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_occluded_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    dev::OcclusionParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    dev::KParams& P = Q.K;
+    fill_scene_tables(P, S);
+    P.counters = (unsigned long long*)a->counters;
+    P.regen_threshold = (uint32_t)g_regen_threshold;
+    P.regen_live_frac = (uint32_t)g_regen_live_frac;
+    P.leaf_break = (uint32_t)g_leaf_break;
+    Q.rays = (const float4*)a->rays;
+    Q.occluded = a->occluded;
+    Q.blocker = a->blocker;
+    Q.source = (const int32_t*)S.prim_source;
+    Q.n = a->n;
+    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->n));
+    const uint32_t grid = (uint32_t)((n + Q.per_wave - 1) / Q.per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    const auto kernel = S.wide_refs ? (a->count_tests ? dev::occlusion_rays_kernel<true, true> : dev::occlusion_rays_kernel<false, true>)
+                                    : (a->count_tests ? dev::occlusion_rays_kernel<true, false> : dev::occlusion_rays_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
+    return hip_check(hipGetLastError(), "rt_occluded_rays: kernel launch", RT_ERR_LAUNCH);
 }
 
 int rt_set_pixel_cost(void* buffer, uint64_t bytes) {

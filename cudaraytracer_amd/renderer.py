@@ -88,6 +88,30 @@ class DeviceScene:
         check(lib().rt_query_rays(self.handle, C.byref(a), C.c_void_p(stream)), "rt_query_rays")
         return out
 
+    def occluded(self, rays, blocker: bool = False, rays_per_lane: int = 0):
+        """Is anything hit within each ray's own range (rt_occluded_rays)?  Asynchronous on torch's current stream.
+        rays: (n, 2, 4) float32, (origin, tmin), (direction, tmax) per ray — a torch tensor on the device, or a numpy
+        array (uploaded to the current device); t is in units of |direction|.  Returns a bool (n,) tensor, or with
+        blocker=True the pair (occluded, blocker): int32 (n,), the index in the scene's hittables of a primitive that
+        the ray hits within its range (not necessarily the nearest), -1 where nothing is hit."""
+        if isinstance(rays, np.ndarray):
+            rays = torch.from_numpy(np.array(rays, dtype=np.float32, order="C")).cuda()  # (a copy: the caller's may be read-only)
+        if rays.dtype != torch.float32 or rays.dim() != 3 or tuple(rays.shape[1:]) != (2, 4) or not rays.is_cuda:
+            raise ValueError("rays must be a float32 (n, 2, 4) tensor on the device")
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        occ = torch.empty((n,), dtype=torch.bool, device=rays.device)  # (one byte per element: the kernel writes 0 / 1)
+        blk = torch.empty((n,), dtype=torch.int32, device=rays.device) if blocker else None
+        if n:
+            a = abi.OcclusionArgs()
+            a.rays, a.occluded = rays.data_ptr(), occ.data_ptr()
+            if blocker:
+                a.blocker = blk.data_ptr()
+            a.n, a.rays_per_lane = n, rays_per_lane
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            check(lib().rt_occluded_rays(self.handle, C.byref(a), C.c_void_p(stream)), "rt_occluded_rays")
+        return (occ, blk) if blocker else occ
+
     def close(self) -> None:
         if self.handle:
             lib().rt_scene_destroy(self.handle)

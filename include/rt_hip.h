@@ -187,7 +187,7 @@ const char* rt_version(void);
  * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes.  14: rt_query_rays; rt_gbuffer and
  * rt_trace_rays take scenes with 32-bit BVH references; later additions that change no structure layout, counter
  * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells,
- * rt_set_tile_occlusion, rt_tile_entries_device (a caller asks the library for them by name). */
+ * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays (a caller asks the library for them by name). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
@@ -419,6 +419,42 @@ typedef struct rt_query_args {
     uint32_t reserved;      /* must be 0 */
 } rt_query_args;
 int rt_query_rays(const rt_scene* scene, const rt_query_args* args, rt_stream stream);
+
+/* Visibility of n rays of the caller's, each with a range of its own: is any primitive hit within (tmin, tmax)?  The
+ * any-hit counterpart of rt_query_rays (shadow rays towards a light inside the scene, ambient occlusion cut off at a
+ * radius, "is the path from A to B free"): the traversal stops at the first primitive whose test accepts, and one byte
+ * per ray is written.  Ray i: o = rays[2i].xyz, tmin = rays[2i].w, d = rays[2i + 1].xyz, tmax = rays[2i + 1].w — the
+ * layout rt_query_rays takes, with its two ignored components given a meaning.  d is not normalised: t is in units
+ * of |d|, so a ray from P with d = L - P and tmax = 1 ends at L.
+ *   !(tmin <= tmax) (a NaN at either end included): unoccluded (0, -1); no traversal starts, and the ray is not counted
+ *   in counters[0].  Otherwise occluded[i] = 1 exactly when some active hittable's own Hit(o, d, tmin, tmax) accepts,
+ *   with the rules of the closest-hit calls: a sphere's near root, then its far root, each for tmin < t < tmax
+ *   (Hittable.cuh:80-110); a rectangle for tmin <= t <= tmax inside its extent (Hittable.cuh:155-166).  tmax may be
+ *   FLT_MAX or +inf, tmin may be 0 or negative.  Rays with a non-finite origin or direction component get an
+ *   unspecified value (and touch no memory but the scene's tables and their own elements).
+ *   blocker[i]: the index in rt_scene_desc.hittables (rt_gbuffer's prim_id meaning) of the primitive that ended the
+ *   ray's traversal — some primitive the ray hits within its range, not necessarily the nearest — or -1.
+ * The range never shrinks during a traversal, so the primitive that ends it depends on the ray alone: both outputs are
+ * the same bits for every rays_per_lane, every rt_set_tuning value and across calls.  One asynchronous launch on
+ * `stream`; every element is written once, by the lane that traced the ray (occluded with a byte store).
+ * RT_ERR_INVALID_ARGUMENT, before any device call and before the scene is read: NULL scene, NULL args, NULL rays with
+ * n > 0, neither occluded nor blocker, count_tests other than 0 or 1 or 1 without counters, rays_per_lane above 16,
+ * non-zero flags or reserved, an output (counters included) that overlaps `rays` or another output.  n = 0: RT_OK.
+ * An empty scene gives all 0 / -1.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED ("BVH too deep"). */
+typedef struct rt_occlusion_args {
+    const float* rays;     /* device, n x 2 float4: (origin.xyz, tmin), (direction.xyz, tmax) */
+    uint8_t*  occluded;    /* optional device uint8[n]: 1 = something is hit within the range, 0 = nothing */
+    int32_t*  blocker;     /* optional device int32[n]: index in rt_scene_desc.hittables of the primitive that
+                              ended the ray's traversal (rt_gbuffer's prim_id meaning), -1 where occluded is 0 */
+    uint64_t* counters;    /* optional device uint64[RT_COUNTERS_WORDS], as rt_trace_rays ([0] rays; with
+                              count_tests also box / primitive tests and wave iterations) */
+    uint32_t n;
+    uint32_t rays_per_lane; /* 0 = automatic (rt_trace_rays' rule), 1..16, as rt_query_args */
+    uint32_t count_tests;   /* 0 or 1 */
+    uint32_t flags;         /* must be 0 */
+    uint32_t reserved[2];   /* must be 0 */
+} rt_occlusion_args;
+int rt_occluded_rays(const rt_scene* scene, const rt_occlusion_args* args, rt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* First-hit G-buffer and edge-avoiding denoiser for low-spp frames.  The reference has neither: while */

@@ -48,6 +48,8 @@ EXPORTED = [
     "rt_trace_rays",
     "rt_query_rays",
     "rt_occluded_rays",
+    "rt_camera_rays",
+    "rt_radiance_rays",
     "rt_gbuffer",
     "rt_denoise",
     "rt_denoise_scratch_bytes",
@@ -120,6 +122,9 @@ def _declare(lib: C.CDLL) -> None:
         lib.rt_query_rays.argtypes = [vp, P(abi.QueryArgs), vp]
     if LIB_PATH == _IN_TREE or hasattr(lib, "rt_occluded_rays"):  # (likewise)
         lib.rt_occluded_rays.argtypes = [vp, P(abi.OcclusionArgs), vp]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_radiance_rays"):  # (likewise)
+        lib.rt_camera_rays.argtypes = [P(abi.CameraRaysArgs), vp]
+        lib.rt_radiance_rays.argtypes = [vp, P(abi.RadianceArgs), vp]
     lib.rt_gbuffer.argtypes = [vp, P(abi.GBufferArgs), vp]
     lib.rt_denoise.argtypes = [P(abi.DenoiseArgs), vp]
     lib.rt_denoise_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]

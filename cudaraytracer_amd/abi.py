@@ -22,6 +22,7 @@ RT_FLAG_COUNT_TESTS = 1 << 4
 RT_FLAG_RNG_PHILOX = 1 << 5
 RT_FLAG_STATE_SOA = 1 << 6
 RT_FLAG_ACCUMULATE_RESET = 1 << 7
+RT_CAMERA_JITTER_PHILOX = 1 << 0
 RT_DENOISE_DEMODULATE = 1 << 0
 RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
@@ -29,8 +30,8 @@ RT_TEMPORAL_RESET = 1 << 1
 # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host;
 # 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP; 13: rt_temporal_moments, rt_denoise_variance,
 # rt_denoise_variance_scratch_bytes; 14: rt_query_rays, 32-bit references in rt_gbuffer and rt_trace_rays
-# (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells and rt_occluded_rays were added without a new
-# number: no layout changed)
+# (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells, rt_occluded_rays, rt_camera_rays and
+# rt_radiance_rays were added without a new number: no layout changed)
 ABI_VERSION = 14
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
@@ -219,6 +220,53 @@ class OcclusionArgs(C.Structure):  # rt_occlusion_args
         ("count_tests", C.c_uint32),
         ("flags", C.c_uint32),
         ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class CameraRaysArgs(C.Structure):
+    """rt_camera_rays_args, 160 bytes."""
+
+    _fields_ = [
+        ("rays", C.c_void_p),
+        ("pixels", C.c_void_p),
+        ("pixel_index", C.c_void_p),
+        ("n", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("tiling", Tiling),
+        ("inputs", InputStruct),
+        ("xi1", C.c_float),
+        ("xi2", C.c_float),
+        ("rng_seed", C.c_uint64),
+        ("rng_frame", C.c_uint32),
+        ("sample", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class RadianceArgs(C.Structure):
+    """rt_radiance_args, 120 bytes."""
+
+    _fields_ = [
+        ("rays", C.c_void_p),
+        ("stream_ids", C.c_void_p),
+        ("sum", C.c_void_p),
+        ("mean", C.c_void_p),
+        ("counters", C.c_void_p),
+        ("n", C.c_uint32),
+        ("rays_per_lane", C.c_uint32),
+        ("samples_per_ray", C.c_uint32),
+        ("sample_base", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("count_tests", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("stream_base", C.c_uint32),
+        ("rng_seed", C.c_uint64),
+        ("rng_frame", C.c_uint32),
+        ("background_start", F3),
+        ("background_end", F3),
+        ("reserved", C.c_uint32 * 3),
     ]
 
 

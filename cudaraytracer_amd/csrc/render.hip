@@ -4126,6 +4126,176 @@ __global__ __launch_bounds__(64, 4) void occlusion_rays_kernel(const OcclusionPa
     flush_counts<COUNT_TESTS>(*P, cnt);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Path-traced radiance per ray (rt_radiance_rays): query_rays_kernel's schedule with color()'s bounce loop in the
+// shading step.  A lane owns one ray of the batch for all its samples: MODE_SHADE calls shade() on the Philox stream
+// (key, subsequence id, frame); a path that continues restarts the traversal, one that ends goes into the lane's three
+// 2^-12 fixed-point sums, and the lane then reloads its own ray for the next sample or stores and takes the wave's
+// next ray.  Sample s of a ray draws from block ((sample_base + s) << 16) + 1 on: block 0 of the window is the camera
+// jitter's (camera_ray), which rt_camera_rays reads.  The closest hit is the geometric one (rt_trace_rays' semantics);
+// the sums are order-free and every element is written by the lane that traced the ray, so the result does not depend
+// on the schedule.  The params begin with a KParams: shade() and philox_block() read the kernel arguments as one.
+// ---------------------------------------------------------------------------------------------------
+struct RadianceParams {
+    KParams K;
+    const float4* rays;
+    const uint32_t* stream_ids;
+    float4* sum;
+    float4* mean;
+    uint32_t n, per_wave;
+    uint32_t samples, sample_base, stream_base;
+};
+static_assert(offsetof(RadianceParams, K) == 0, "philox_block and kparams_reload read the kernel arguments as a KParams");
+
+template <bool COUNT_TESTS, bool WIDE>
+__global__ __launch_bounds__(64, 4) void radiance_rays_kernel(const RadianceParams Q) {
+    using Entry = typename RefW<WIDE>::Entry;
+    const KParams* P = &Q.K;
+    extern __shared__ float4 lds[];
+    const uint32_t lane = threadIdx.x & 63u;
+    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
+    const __amdgpu_buffer_rsrc_t nrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+    stk[0] = (Entry)RefW<WIDE>::kSentinel;
+    stk[64] = (Entry)RefW<WIDE>::kSentinel;
+    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
+    const uint32_t count = min(Q.n - base, Q.per_wave);  // rays of this wave's range (base + per_wave may wrap)
+    Counts cnt{0, 0, 0, 0, 0, 0, 0};
+    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+    uint32_t ray = base + lane, nrays = 0u, npaths = 0u;
+    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
+    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the ray's sample sums, 2^-12 units
+    uint32_t sample = 0u, depth = 0u;
+    RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
+    const bool rtl = P->rius_rtl != 0;
+    // the lane's ray starts its path of sample `sample`
+    const auto begin_path = [&]() {
+        const float4 o = Q.rays[2 * (size_t)ray], d = Q.rays[2 * (size_t)ray + 1];
+        ro = xyz(o);
+        rd = xyz(d);
+        att = mk(1.0f, 1.0f, 1.0f);
+        depth = 0u;
+        rng.n = ((Q.sample_base + sample) << 16) + 1u;
+        npaths++;
+        v3_start_trace<WIDE>(P->num_nodes, c, nrays);
+    };
+    const auto store = [&]() {
+        const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
+        const float ns = (float)Q.samples;
+        if (Q.sum) Q.sum[ray] = make_float4(s.x, s.y, s.z, ns);
+        if (Q.mean) {
+            const f3 m = divs_rn(s, ns, recip_in_range(ns));  // write_pixel's division
+            Q.mean[ray] = make_float4(m.x, m.y, m.z, 1.0f);
+        }
+        c.mode = MODE_NEED;
+    };
+    const auto start = [&](uint32_t i) {
+        ray = i;
+        rng.pix = Q.stream_ids ? Q.stream_ids[i] : Q.stream_base + i;
+        q0 = q1 = q2 = 0u;
+        sample = 0u;
+        if (P->max_depth != 0u) {
+            begin_path();
+        } else {  // exceeded recursion at once (Kernel.cu:79): every sample is 0, nothing is traced
+            npaths += Q.samples;
+            c.mode = MODE_ENDED;
+        }
+    };
+    if (lane < count) start(ray);
+    uint32_t taken = 64u;  // wave-uniform: rays of the wave's range handed out so far
+    while (__ballot(c.mode != MODE_DONE) != 0) {
+        if (c.mode == MODE_TRAV) {
+            uint32_t thr = P->regen_threshold;
+            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c, cnt, 64u,
+                                                                P->leaf_break);
+        }
+        if (c.mode == MODE_SHADE) {
+            if (COUNT_TESTS) cnt.wshade += wave_leader();
+            KParamsC* const q = kparams_reload();
+            f3 contrib;
+            const int res = shade<true, false, false>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att, rng, rtl,
+                                                      contrib);
+            bool ended = res == SHADE_ENDED;
+            if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
+                ended = true;
+                contrib = mk(0.0f, 0.0f, 0.0f);
+            }
+            if (!ended) {
+                v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+            } else {
+                q0 = sat_add(q0, quant12(contrib.x));
+                q1 = sat_add(q1, quant12(contrib.y));
+                q2 = sat_add(q2, quant12(contrib.z));
+                if (++sample < Q.samples) begin_path();
+                else c.mode = MODE_ENDED;
+            }
+        }
+        if (c.mode == MODE_ENDED) store();
+        const uint64_t needm = __ballot(c.mode == MODE_NEED);
+        if (needm != 0) {
+            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
+            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
+            if (c.mode == MODE_NEED) {
+                if (k < count) start(base + k);
+                else c.mode = MODE_DONE;
+            }
+        }
+    }
+    cnt.rays = nrays;
+    cnt.primary = npaths;
+    flush_counts<COUNT_TESTS>(*P, cnt);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The camera rays of the render kernels as a ray batch (rt_camera_rays): one lane per ray, camera_ray / camera_ray_at
+// and lane_camera themselves.  rays[2i] = (origin, kTmin), rays[2i + 1] = (direction, FLT_MAX): color()'s range.  The
+// params begin with a KParams (camera_ray's Philox draw reads key and frame through the kernel-argument pointer).
+// ---------------------------------------------------------------------------------------------------
+struct CameraRaysParams {
+    KParams K;
+    float4* rays;
+    const uint32_t* pixels;
+    uint32_t* pixel_index;
+    uint32_t n, philox, sample;
+    float xi1, xi2;
+};
+static_assert(offsetof(CameraRaysParams, K) == 0, "philox_block reads the kernel arguments as a KParams");
+
+__global__ __launch_bounds__(kBlock) void camera_rays_kernel(const CameraRaysParams Q) {
+    const KParams* P = &Q.K;
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= Q.n) return;
+    uint32_t x, g, p;
+    if (Q.pixels) {
+        p = Q.pixels[i];
+        if ((uint64_t)p >= (uint64_t)P->width * P->height) {  // outside the frame: an empty range
+            Q.rays[2 * (size_t)i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+            Q.rays[2 * (size_t)i + 1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (Q.pixel_index) Q.pixel_index[i] = p;
+            return;
+        }
+        g = p / P->width;
+        x = p - g * P->width;
+    } else {
+        const uint32_t ly = i / P->width;
+        x = i - ly * P->width;
+        g = global_row(*P, ly);
+        p = g * P->width + x;
+    }
+    f3 ro, rd;
+    if (Q.philox) {
+        KParamsC* const q = kparams_reload();
+        RngPhilox rng = begin_rng<RngPhilox>(nullptr, 0u, p);
+        camera_ray(q, lane_camera(q, x, g), rng, ro, rd, Q.sample);
+    } else {
+        camera_ray_at(P, lane_camera(P, x, g), Q.xi1, Q.xi2, ro, rd);
+    }
+    Q.rays[2 * (size_t)i] = make_float4(ro.x, ro.y, ro.z, kTmin);
+    Q.rays[2 * (size_t)i + 1] = make_float4(rd.x, rd.y, rd.z, FLT_MAX);
+    if (Q.pixel_index) Q.pixel_index[i] = p;
+}
+
 __global__ __launch_bounds__(kBlock) void render_init_kernel(uint32_t* state, uint32_t width, uint32_t local_rows,
                                                               uint32_t band_rows, uint32_t num_ranks, uint32_t rank,
                                                               unsigned long long seed_base, uint32_t soa) {  // soa: plane size
@@ -5093,6 +5263,124 @@ int rt_occluded_rays(const rt_scene* scene, const rt_occlusion_args* a, rt_strea
                                     : (a->count_tests ? dev::occlusion_rays_kernel<true, false> : dev::occlusion_rays_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
     return hip_check(hipGetLastError(), "rt_occluded_rays: kernel launch", RT_ERR_LAUNCH);
+}
+
+int rt_camera_rays(const rt_camera_rays_args* a, rt_stream stream) {
+    // (every argument check runs before the first device call)
+    const auto bad = [](const char* what) {
+        set_error(std::string("rt_camera_rays: ") + what);
+        return RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!a) return bad("NULL args");
+    if ((a->flags & ~RT_CAMERA_JITTER_PHILOX) != 0 || a->reserved[0] != 0 || a->reserved[1] != 0)
+        return bad("unknown flags, or reserved not 0");
+    const bool philox = (a->flags & RT_CAMERA_JITTER_PHILOX) != 0;
+    if (philox && a->sample >= RT_PHILOX_MAX_SPP) return bad("sample must be below RT_PHILOX_MAX_SPP (16384)");
+    const uint64_t n = a->n;
+    if (!a->pixels) {
+        if (!tiling_ok(a->tiling)) return bad("invalid tiling");
+        if (n != (uint64_t)a->tiling.local_rows * a->width) return bad("n is not local_rows * width");
+        if (n != 0 && check_last_row("rt_camera_rays", a->tiling, a->height) != RT_OK) return RT_ERR_INVALID_ARGUMENT;
+    }
+    if (n == 0) return RT_OK;  // nothing to write
+    if (!a->rays) return bad("NULL rays");
+    if (overlaps(a->rays, n * 32u, a->pixels, n * 4u) || overlaps(a->pixel_index, n * 4u, a->pixels, n * 4u))
+        return bad("an output overlaps pixels");
+    if (overlaps(a->rays, n * 32u, a->pixel_index, n * 4u)) return bad("outputs overlap each other");
+    dev::CameraRaysParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    dev::KParams& P = Q.K;
+    if (a->pixels) {  // (global indices: one band of the whole frame, so that every field has a defined value)
+        P.width = a->width;
+        P.height = a->height;
+        P.band_rows = 1u;
+        P.num_ranks = 1u;
+    } else {
+        fill_frame(P, a->width, a->height, a->tiling, false);
+    }
+    if (a->width != 0 && a->height != 0) fill_camera(P, a->inputs, a->width, a->height);
+    P.rng_key_lo = (uint32_t)a->rng_seed;
+    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
+    P.rng_frame = a->rng_frame;
+    Q.rays = (float4*)a->rays;
+    Q.pixels = a->pixels;
+    Q.pixel_index = a->pixel_index;
+    Q.n = a->n;
+    Q.philox = philox ? 1u : 0u;
+    Q.sample = a->sample;
+    Q.xi1 = a->xi1;
+    Q.xi2 = a->xi2;
+    const uint32_t grid = (uint32_t)((n + dev::kBlock - 1) / dev::kBlock);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(dev::camera_rays_kernel, dim3(grid), dim3(dev::kBlock), 0, s, Q);
+    return hip_check(hipGetLastError(), "rt_camera_rays: kernel launch", RT_ERR_LAUNCH);
+}
+
+int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* a, rt_stream stream) {
+    // (every argument check runs before the first device call and before the scene is read)
+    const auto bad = [](const char* what) {
+        set_error(std::string("rt_radiance_rays: ") + what);
+        return RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!a) return bad("NULL args");
+    if ((a->flags & ~(uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT) != 0) return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT");
+    if (a->reserved[0] != 0 || a->reserved[1] != 0 || a->reserved[2] != 0) return bad("reserved must be 0");
+    if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
+    if (a->count_tests > 1u) return bad("count_tests must be 0 or 1");
+    if (a->count_tests && !a->counters) return bad("count_tests without counters");
+    if (!a->sum && !a->mean) return bad("no output buffer");
+    if (a->samples_per_ray == 0u) return bad("samples_per_ray must be at least 1");
+    if ((uint64_t)a->sample_base + a->samples_per_ray > RT_PHILOX_MAX_SPP)
+        return bad("sample_base + samples_per_ray above RT_PHILOX_MAX_SPP (16384)");
+    const uint64_t n = a->n;
+    if (n == 0) return RT_OK;  // nothing to trace
+    if (!a->rays) return bad("NULL rays");
+    const void* const outs[3] = {a->sum, a->mean, a->counters};
+    const uint64_t out_bytes[3] = {n * 16u, n * 16u, (uint64_t)RT_COUNTERS_WORDS * 8u};
+    for (int o = 0; o < 3; o++) {
+        if (overlaps(outs[o], out_bytes[o], a->rays, n * 32u)) return bad("an output overlaps rays");
+        if (overlaps(outs[o], out_bytes[o], a->stream_ids, n * 4u)) return bad("an output overlaps stream_ids");
+        for (int p = 0; p < o; p++)
+            if (overlaps(outs[o], out_bytes[o], outs[p], out_bytes[p])) return bad("outputs overlap each other");
+    }
+    if (!scene) return bad("NULL scene");
+    const DeviceScene& S = scene->dev;
+    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
+    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_radiance_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    dev::RadianceParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    dev::KParams& P = Q.K;
+    fill_scene_tables(P, S);
+    P.counters = (unsigned long long*)a->counters;
+    P.regen_threshold = (uint32_t)g_regen_threshold;
+    P.regen_live_frac = (uint32_t)g_regen_live_frac;
+    P.leaf_break = (uint32_t)g_leaf_break;
+    P.max_depth = a->max_depth;
+    P.rius_rtl = (a->flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
+    P.rng_key_lo = (uint32_t)a->rng_seed;
+    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
+    P.rng_frame = a->rng_frame;
+    for (int i = 0; i < 3; i++) {
+        P.bg0[i] = a->background_start[i];
+        P.bg1[i] = a->background_end[i];
+    }
+    Q.rays = (const float4*)a->rays;
+    Q.stream_ids = a->stream_ids;
+    Q.sum = (float4*)a->sum;
+    Q.mean = (float4*)a->mean;
+    Q.n = a->n;
+    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->n));
+    Q.samples = a->samples_per_ray;
+    Q.sample_base = a->sample_base;
+    Q.stream_base = a->stream_base;
+    const uint32_t grid = (uint32_t)((n + Q.per_wave - 1) / Q.per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    const auto kernel = S.wide_refs ? (a->count_tests ? dev::radiance_rays_kernel<true, true> : dev::radiance_rays_kernel<false, true>)
+                                    : (a->count_tests ? dev::radiance_rays_kernel<true, false> : dev::radiance_rays_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
+    return hip_check(hipGetLastError(), "rt_radiance_rays: kernel launch", RT_ERR_LAUNCH);
 }
 
 int rt_set_pixel_cost(void* buffer, uint64_t bytes) {

@@ -112,6 +112,47 @@ class DeviceScene:
             check(lib().rt_occluded_rays(self.handle, C.byref(a), C.c_void_p(stream)), "rt_occluded_rays")
         return (occ, blk) if blocker else occ
 
+    def radiance(self, rays, samples: int = 1, depth: int = 8, sample_base: int = 0, stream_ids=None, seed: int = 1984,
+                 frame: int = 0, background=((1.0, 1.0, 1.0), (0.5, 0.7, 1.0)), mean: bool = True, rays_per_lane: int = 0,
+                 left_to_right: bool = False):
+        """Path-traced radiance along rays of the caller's own (rt_radiance_rays), asynchronous on torch's current
+        stream.  rays: (n, 2, 4) float32, (origin, -), (direction, -) per ray — a torch tensor on the device, or a numpy
+        array (uploaded to the current device).  Ray i takes `samples` paths of at most `depth` bounces on the Philox
+        stream (seed, stream_ids[i] or i, frame), samples sample_base .. sample_base + samples - 1.  stream_ids: a
+        uint32 / int32 (n,) device tensor (the values' 32 bits are the ids), e.g. camera_rays' pixel_index.
+        background: (start, end) of the sky's blend.  Returns a float32 (n, 4) tensor: mean=True (r, g, b, 1), the
+        average of the samples; mean=False (r, g, b, samples), their fixed-point sum, which adds into an accumulation
+        buffer as a frame's samples do."""
+        if isinstance(rays, np.ndarray):
+            rays = torch.from_numpy(np.array(rays, dtype=np.float32, order="C")).cuda()  # (a copy: the caller's may be read-only)
+        if rays.dtype != torch.float32 or rays.dim() != 3 or tuple(rays.shape[1:]) != (2, 4) or not rays.is_cuda:
+            raise ValueError("rays must be a float32 (n, 2, 4) tensor on the device")
+        rays = rays.contiguous()
+        n = rays.shape[0]
+        if stream_ids is not None:
+            if (stream_ids.dtype not in (torch.int32, torch.uint32) or tuple(stream_ids.shape) != (n,)
+                    or stream_ids.device != rays.device):
+                raise ValueError("stream_ids must be a 32-bit integer (n,) tensor on the rays' device")
+            stream_ids = stream_ids.contiguous()
+        out = torch.empty((n, 4), dtype=torch.float32, device=rays.device)
+        if n:
+            a = abi.RadianceArgs()
+            a.rays = rays.data_ptr()
+            if mean:
+                a.mean = out.data_ptr()
+            else:
+                a.sum = out.data_ptr()
+            if stream_ids is not None:
+                a.stream_ids = stream_ids.data_ptr()
+            a.n, a.rays_per_lane, a.samples_per_ray, a.sample_base, a.max_depth = n, rays_per_lane, samples, sample_base, depth
+            a.flags = abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0
+            a.rng_seed, a.rng_frame = seed, frame
+            a.background_start[:] = [float(v) for v in background[0]]
+            a.background_end[:] = [float(v) for v in background[1]]
+            stream = torch.cuda.current_stream(rays.device).cuda_stream
+            check(lib().rt_radiance_rays(self.handle, C.byref(a), C.c_void_p(stream)), "rt_radiance_rays")
+        return out
+
     def close(self) -> None:
         if self.handle:
             lib().rt_scene_destroy(self.handle)
@@ -131,6 +172,46 @@ def set_tile_occlusion(on: bool) -> bool:
     if prev < 0:
         check(prev, "rt_set_tile_occlusion")
     return bool(prev)
+
+
+def camera_rays(inputs: abi.InputStruct, width: int, height: int, pixels=None, jitter=(0.5, 0.5), sample: int = 0,
+                seed: int = 1984, frame: int = 0, tiling: abi.Tiling | None = None, device=None):
+    """The library's own camera rays as a ray batch (rt_camera_rays), asynchronous on torch's current stream: the rays
+    the render kernels trace, bit for bit.  pixels=None: one ray per pixel of the frame, row-major (of this rank's
+    rows with a `tiling`); pixels: a 32-bit integer (n,) device tensor (or a sequence, uploaded) of global pixel
+    indices y * width + x, one ray each.  jitter: a pair (xi1, xi2) in pixel units — (0.5, 0.5) is the pixel centre,
+    rt_gbuffer's ray — or "philox": the jitter rt_render draws for that pixel's sample `sample` with
+    RT_FLAG_RNG_PHILOX, seed and frame.  Returns (rays, pixel_index): float32 (n, 2, 4) as (origin, 0.001),
+    (direction, FLT_MAX) — valid for DeviceScene.query, .occluded and .radiance as it is — and int32 (n,), each ray's
+    global pixel index (DeviceScene.radiance's stream_ids)."""
+    if pixels is not None and not isinstance(pixels, torch.Tensor):
+        pixels = torch.from_numpy(np.array(pixels, dtype=np.int64).astype(np.uint32).view(np.int32)).cuda()
+    if pixels is not None:
+        if pixels.dtype not in (torch.int32, torch.uint32) or pixels.dim() != 1 or not pixels.is_cuda:
+            raise ValueError("pixels must be a 32-bit integer (n,) tensor on the device")
+        pixels = pixels.contiguous()
+        device = pixels.device
+    elif device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    t = tiling if tiling is not None else abi.Tiling(max(height, 1), 1, 0, height)
+    n = pixels.shape[0] if pixels is not None else t.local_rows * width
+    rays = torch.empty((n, 2, 4), dtype=torch.float32, device=device)
+    index = torch.empty((n,), dtype=torch.int32, device=device)
+    if n:
+        a = abi.CameraRaysArgs()
+        a.rays, a.pixel_index = rays.data_ptr(), index.data_ptr()
+        if pixels is not None:
+            a.pixels = pixels.data_ptr()
+        a.n, a.width, a.height, a.tiling, a.inputs = n, width, height, t, inputs
+        if isinstance(jitter, str):
+            if jitter != "philox":
+                raise ValueError('jitter must be a pair (xi1, xi2) or "philox"')
+            a.flags, a.sample, a.rng_seed, a.rng_frame = abi.RT_CAMERA_JITTER_PHILOX, sample, seed, frame
+        else:
+            a.xi1, a.xi2 = float(jitter[0]), float(jitter[1])
+        stream = torch.cuda.current_stream(device).cuda_stream
+        check(lib().rt_camera_rays(C.byref(a), C.c_void_p(stream)), "rt_camera_rays")
+    return rays, index
 
 
 def band_rows_of(height: int, band_rows: int, num_ranks: int, rank: int) -> list[int]:

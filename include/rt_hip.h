@@ -187,7 +187,8 @@ const char* rt_version(void);
  * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes.  14: rt_query_rays; rt_gbuffer and
  * rt_trace_rays take scenes with 32-bit BVH references; later additions that change no structure layout, counter
  * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells,
- * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays (a caller asks the library for them by name). */
+ * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays, rt_camera_rays, rt_radiance_rays (a caller asks the
+ * library for them by name). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
@@ -455,6 +456,86 @@ typedef struct rt_occlusion_args {
     uint32_t reserved[2];   /* must be 0 */
 } rt_occlusion_args;
 int rt_occluded_rays(const rt_scene* scene, const rt_occlusion_args* args, rt_stream stream);
+
+/* The reference's camera rays (Kernel.cu:139-146) in the ray-batch layout, written by the render kernels' own device
+ * code: rays[2i] = (origin, 0.001f), rays[2i + 1] = (direction, FLT_MAX) — the .w values are color()'s range, so the
+ * batch is valid for rt_occluded_rays as it is (rt_query_rays, rt_trace_rays and rt_radiance_rays ignore .w).
+ *   pixels == NULL: ray i belongs to local pixel i of the tiling (row-major over local_rows x width, the global row as
+ *   rt_gbuffer maps it); n must equal local_rows * width.
+ *   pixels given: ray i belongs to the global pixel pixels[i] = g * width + x (the sparse form: chosen pixels, in any
+ *   order, duplicates allowed; the tiling is not read).  An index >= width * height gives the ray (0, 0, 0, 1),
+ *   (0, 0, 0, 0): an empty range, nothing else is touched.
+ *   pixel_index[i]: the global pixel index of ray i (pixels[i] itself in the sparse form) — the stream id
+ *   rt_radiance_rays takes.
+ * Jitter: flags = 0: the fixed pair (xi1, xi2) for every ray; (0.5f, 0.5f) is rt_gbuffer's ray.
+ * RT_CAMERA_JITTER_PHILOX: words 0 and 1 of block sample << 16 of the stream (rng_seed, pixel, rng_frame) — the ray
+ * rt_render traces for that pixel's sample `sample` with RT_FLAG_RNG_PHILOX; sample < RT_PHILOX_MAX_SPP.
+ * One asynchronous launch on `stream`; every element is written once by one lane.  RT_ERR_INVALID_ARGUMENT, before any
+ * device call: NULL args, NULL rays with n > 0, an n that does not fit the tiling (or an invalid tiling) with pixels
+ * NULL, unknown flag bits, non-zero reserved words, sample out of range, an output that overlaps `pixels` or the other
+ * output.  n = 0: RT_OK. */
+#define RT_CAMERA_JITTER_PHILOX 1u
+typedef struct rt_camera_rays_args {
+    float* rays;              /* out, device, n x 2 float4 */
+    const uint32_t* pixels;   /* optional device uint32[n]: global pixel indices g * width + x */
+    uint32_t* pixel_index;    /* optional out, device uint32[n] */
+    uint32_t n;
+    uint32_t width, height;
+    uint32_t flags;           /* 0 or RT_CAMERA_JITTER_PHILOX */
+    rt_tiling tiling;         /* read when pixels is NULL */
+    rt_input_struct inputs;
+    float xi1, xi2;           /* the jitter pair without RT_CAMERA_JITTER_PHILOX */
+    uint64_t rng_seed;        /* RT_CAMERA_JITTER_PHILOX: as rt_render_args */
+    uint32_t rng_frame;
+    uint32_t sample;          /* RT_CAMERA_JITTER_PHILOX: the sample whose jitter group is read */
+    uint32_t reserved[2];     /* must be 0 */
+} rt_camera_rays_args;        /* 160 B */
+int rt_camera_rays(const rt_camera_rays_args* args, rt_stream stream);
+
+/* Path-traced radiance along n rays of the caller's: how much light arrives along each.  For ray i (o = rays[2i].xyz,
+ * d = rays[2i + 1].xyz, .w ignored) and sample s in [0, samples_per_ray): c_s = color(o, d, max_depth) (Kernel.cu:30-80)
+ * as the render kernels compute it in Philox mode, each closest hit with rt_trace_rays' semantics (the geometric closest
+ * hit for t in (0.001, FLT_MAX), no reference replay).  The draws come from the stream (rng_seed, subsequence id_i,
+ * rng_frame), id_i = stream_ids ? stream_ids[i] : stream_base + i, in the window of sample sample_base + s starting at
+ * the window's block 1 (block 0 is the camera-jitter group rt_render draws and rt_camera_rays reads).  The samples are
+ * summed in 2^-12 fixed point, saturating, as RT_FLAG_RNG_PHILOX frames are:
+ *   sum[i]  = (q / 4096, samples_per_ray)            — what RT_FLAG_ACCUMULATE adds to an accumulation buffer
+ *   mean[i] = (q / 4096 / samples_per_ray, 1)        — rt_render's radiance
+ * So a ray from rt_camera_rays(RT_CAMERA_JITTER_PHILOX, sample = s) with its pixel index as id and sample_base = s gives
+ * exactly the sample a Philox frame adds for that pixel; k samples in one call equal the fixed-point sum of k
+ * one-sample calls; and neither output depends on rays_per_lane, on rt_set_tuning or on the call.
+ * counters[0]: color() iterations (rays traced; a path at the depth limit ends with 0 and no trace), counters[3]:
+ * n * samples_per_ray; with count_tests the box / primitive tests and wave iterations, as rt_trace_rays.
+ * flags: 0 or RT_FLAG_RIUS_LEFT_TO_RIGHT.  background_start / background_end: the sky of Kernel.cu:41-44.  There is no
+ * XORWOW mode (a per-ray call has no per-ray state buffer).  d need not be normalised; rays with a zero or non-finite
+ * component get an unspecified value and touch only the scene's tables and their own elements.
+ * One asynchronous launch on `stream`; every element is written once, by the lane that traced the ray.
+ * RT_ERR_INVALID_ARGUMENT, before any device call and before the scene is read: NULL scene, NULL args, NULL rays with
+ * n > 0, neither sum nor mean, rays_per_lane above 16, samples_per_ray = 0 or sample_base + samples_per_ray above
+ * RT_PHILOX_MAX_SPP, count_tests other than 0 or 1 or 1 without counters, other flag bits, non-zero reserved words, an
+ * output (counters included) that overlaps rays, stream_ids or another output.  n = 0: RT_OK.  max_depth = 0: sums of
+ * 0.  An empty scene gives the sky for every ray.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED. */
+typedef struct rt_radiance_args {
+    const float* rays;          /* device, n x 2 float4: (origin.xyz, -), (direction.xyz, -) */
+    const uint32_t* stream_ids; /* optional device uint32[n]: the Philox subsequence of each ray */
+    float* sum;                 /* optional out, device float4[n] */
+    float* mean;                /* optional out, device float4[n] */
+    uint64_t* counters;         /* optional device uint64[RT_COUNTERS_WORDS] (added to, not cleared) */
+    uint32_t n;
+    uint32_t rays_per_lane;     /* 0 = automatic, 1..16, as rt_query_args (1 suits several samples per ray) */
+    uint32_t samples_per_ray;   /* >= 1 */
+    uint32_t sample_base;
+    uint32_t max_depth;
+    uint32_t count_tests;       /* 0 or 1 */
+    uint32_t flags;             /* 0 or RT_FLAG_RIUS_LEFT_TO_RIGHT */
+    uint32_t stream_base;       /* without stream_ids: ray i draws from subsequence stream_base + i */
+    uint64_t rng_seed;
+    uint32_t rng_frame;
+    float background_start[3];
+    float background_end[3];
+    uint32_t reserved[3];       /* must be 0 */
+} rt_radiance_args;             /* 120 B */
+int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* args, rt_stream stream);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* First-hit G-buffer and edge-avoiding denoiser for low-spp frames.  The reference has neither: while */

@@ -2,7 +2,7 @@
 BASELINE config 2 (the 488-sphere RTIOW scene, 16-bit BVH references), then on sphere_field(9000, 6) (32-bit references)
 under the same camera, 1920x1080.
 
-Batch (a): the frame's camera centre rays (tools/bench_query.py's, computed in numpy and uploaded once) with the range
+Batch (a): the frame's camera centre rays (tools/bench_query.py's, written once by rt_camera_rays) with the range
 (0.001, FLT_MAX): rt_occluded_rays with `occluded` only against rt_query_rays with `hits` only on the same buffer, with
 the same rays_per_lane — automatic and 1 — the two calls alternating in one session.
 Batch (b): shadow rays from the G-buffer's hit points (P = o + t·d with t from rt_query_rays' normal_depth) towards the
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 from cudaraytracer_amd import abi, scenes
 from cudaraytracer_amd._lib import check, lib
-from cudaraytracer_amd.renderer import DeviceScene
+from cudaraytracer_amd.renderer import DeviceScene, camera_rays
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--calls", type=int, default=50, help="timed calls (the median is reported)")
@@ -37,27 +37,6 @@ F = np.float32
 FLT_MAX = float(np.finfo(F).max)
 LIGHT = (2.0, 5.0, 3.0)
 
-
-def centre_rays(inp: abi.InputStruct, width: int, height: int) -> np.ndarray:
-    """(height * width, 2, 4) float32: (origin, 0.001), (direction, FLT_MAX) of the pixel-centre camera rays."""
-    v3 = lambda a: np.array([a[0], a[1], a[2]], dtype=F)
-    up, fw, origin = v3(inp.up), v3(inp.orientation), v3(inp.origin)
-    cr = np.array([up[1] * fw[2] - up[2] * fw[1], -(up[0] * fw[2] - up[2] * fw[0]), up[0] * fw[1] - up[1] * fw[0]], dtype=F)
-    right = (F(1.0) / np.sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2], dtype=F)) * cr
-    fov, near, far = F(inp.fov), F(inp.near_plane), F(inp.far_plane)
-    k10 = (F(1.0) / fov) * F(10.0)
-    ys, xs = np.mgrid[0:height, 0:width]
-    u = ((xs.astype(F) - F(width) / F(2.0)) + F(0.5)) / F(width)
-    v = ((F(height) / F(2.0) - ys.astype(F)) + F(0.5)) / F(width)
-    dist = u[..., None] * right + v[..., None] * up
-    start = (near * dist + origin) + fov * fw
-    d = ((far * dist + k10 * fw) + origin) - start
-    inv = F(1.0) / np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2], dtype=F)
-    rays = np.zeros((height * width, 2, 4), dtype=F)
-    rays[:, 0, :3] = start.reshape(-1, 3)
-    rays[:, 1, :3] = (inv[..., None] * d).reshape(-1, 3)
-    rays[:, 0, 3], rays[:, 1, 3] = 0.001, FLT_MAX
-    return rays
 
 
 def one_call(fn) -> float:
@@ -80,7 +59,7 @@ def timed(*fns) -> list:
 
 device = torch.device("cuda", 0)
 n = cfg.width * cfg.height
-camera = torch.from_numpy(centre_rays(inputs, cfg.width, cfg.height)).to(device)
+camera, _ = camera_rays(inputs, cfg.width, cfg.height, device=device)  # (origin, 0.001), (direction, FLT_MAX)
 occ = torch.zeros(n, dtype=torch.uint8, device=device)
 hits = torch.zeros((n, 2), dtype=torch.int32, device=device)
 stream = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)

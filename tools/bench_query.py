@@ -2,8 +2,8 @@
 outputs) and rt_gbuffer on one GPU, first on BASELINE config 2 (the 488-sphere RTIOW scene, 16-bit BVH references), then
 on sphere_field(9000, 6) (32-bit references) under the same camera.
 
-The rays are the frame's 1920x1080 camera centre rays, computed in numpy (Kernel.cu:130-146 with both jitter numbers
-0.5) and uploaded once, row-major: a wave's 64 consecutive rays are a 64-pixel piece of one row, where rt_gbuffer gives
+The rays are the frame's 1920x1080 camera centre rays, written once by rt_camera_rays (Kernel.cu:130-146 with both jitter
+numbers 0.5: rt_gbuffer's own rays), row-major: a wave's 64 consecutive rays are a 64-pixel piece of one row, where rt_gbuffer gives
 a wave an 8x8 tile.  Each call is timed with HIP events on one stream: the median of --calls calls after --warmup
 warm-up calls.  Bytes are the compulsory ones: 32 per ray read, plus the outputs written (hits 8; all outputs 16 + 16 +
 4 + 8 + 4 + 8 = 56; rt_gbuffer reads no rays and writes 36).  Prints one JSON line and writes it to --json.
@@ -14,7 +14,7 @@ import numpy as np
 import torch
 from cudaraytracer_amd import abi, scenes
 from cudaraytracer_amd._lib import check, lib
-from cudaraytracer_amd.renderer import DeviceScene, Renderer
+from cudaraytracer_amd.renderer import DeviceScene, Renderer, camera_rays
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--calls", type=int, default=50, help="timed calls (the median is reported)")
@@ -32,26 +32,6 @@ inputs = cfg.inputs()
 F = np.float32
 
 
-def centre_rays(inp: abi.InputStruct, width: int, height: int) -> np.ndarray:
-    """(height * width, 2, 4) float32: (origin, 0), (direction, 0) of the pixel-centre camera rays."""
-    v3 = lambda a: np.array([a[0], a[1], a[2]], dtype=F)
-    up, fw, origin = v3(inp.up), v3(inp.orientation), v3(inp.origin)
-    cr = np.array([up[1] * fw[2] - up[2] * fw[1], -(up[0] * fw[2] - up[2] * fw[0]), up[0] * fw[1] - up[1] * fw[0]], dtype=F)
-    right = (F(1.0) / np.sqrt(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2], dtype=F)) * cr
-    fov, near, far = F(inp.fov), F(inp.near_plane), F(inp.far_plane)
-    k10 = (F(1.0) / fov) * F(10.0)
-    ys, xs = np.mgrid[0:height, 0:width]
-    u = ((xs.astype(F) - F(width) / F(2.0)) + F(0.5)) / F(width)
-    v = ((F(height) / F(2.0) - ys.astype(F)) + F(0.5)) / F(width)
-    dist = u[..., None] * right + v[..., None] * up
-    start = (near * dist + origin) + fov * fw
-    d = ((far * dist + k10 * fw) + origin) - start
-    inv = F(1.0) / np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2], dtype=F)
-    rays = np.zeros((height * width, 2, 4), dtype=F)
-    rays[:, 0, :3] = start.reshape(-1, 3)
-    rays[:, 1, :3] = (inv[..., None] * d).reshape(-1, 3)
-    return rays
-
 
 def timed(fn) -> float:
     t = []
@@ -67,7 +47,7 @@ def timed(fn) -> float:
 
 r = Renderer(cfg.width, cfg.height)
 n = cfg.width * cfg.height
-rays = torch.from_numpy(centre_rays(inputs, cfg.width, cfg.height)).to(r.device)
+rays, _ = camera_rays(inputs, cfg.width, cfg.height, device=r.device)  # jitter (0.5, 0.5): rt_gbuffer's rays, bit for bit
 ALL = tuple(DeviceScene.QUERY_OUTPUTS)
 bufs = {o: torch.zeros((n,) + shape, dtype=dtype, device=r.device) for o, (shape, dtype) in DeviceScene.QUERY_OUTPUTS.items()}
 

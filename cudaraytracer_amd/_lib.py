@@ -78,6 +78,8 @@ EXPORTED = [
     "rt_set_bounce_entries",
     "rt_bounce_entries_host",
     "rt_bounce_entry_cells",
+    "rt_set_bounce_classes",
+    "rt_bounce_class_entries_host",
 ]
 
 _lib = None
@@ -166,6 +168,11 @@ def _declare(lib: C.CDLL) -> None:
         lib.rt_bounce_entries_host.argtypes = [P(abi.SceneDesc), P(C.c_float), P(C.c_float), P(C.c_uint32), P(C.c_uint32),
                                                P(C.c_uint16), P(abi.BounceEntriesInfo)]
         lib.rt_bounce_entry_cells.argtypes = [P(abi.BounceEntriesInfo), P(C.c_float), C.c_uint32, P(C.c_uint32)]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_set_bounce_classes"):  # (an A/B build of an older revision lacks them)
+        lib.rt_set_bounce_classes.argtypes = [C.c_int]
+        lib.rt_bounce_class_entries_host.argtypes = [P(abi.SceneDesc), C.c_int, C.c_uint32, P(C.c_uint32), P(C.c_float),
+                                                     P(C.c_uint32), P(C.c_double), P(C.c_float), P(C.c_float), C.c_uint32,
+                                                     P(C.c_uint32), P(abi.BounceClassInfo)]
     lib.LaunchKernel.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, abi.InputStruct]
     lib.LaunchKernel.restype = None
     lib.LaunchRandInit.argtypes = [vp]

@@ -30,8 +30,9 @@ RT_TEMPORAL_RESET = 1 << 1
 # RT_ABI_VERSION; 9: rt_scene_motion, rt_temporal_dynamic, rt_scene_edit; 10: rt_tile_entries_host;
 # 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP; 13: rt_temporal_moments, rt_denoise_variance,
 # rt_denoise_variance_scratch_bytes; 14: rt_query_rays, 32-bit references in rt_gbuffer and rt_trace_rays
-# (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells, rt_occluded_rays, rt_camera_rays and
-# rt_radiance_rays were added without a new number: no layout changed)
+# (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells, rt_occluded_rays, rt_camera_rays,
+# rt_radiance_rays, rt_set_bounce_classes and rt_bounce_class_entries_host were added without a new number: no layout
+# changed)
 ABI_VERSION = 14
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
@@ -375,6 +376,15 @@ class BounceEntriesInfo(C.Structure):
     _fields_ = [("num_nodes", C.c_uint32), ("num_chain_nodes", C.c_uint32), ("num_records", C.c_uint32),
                 ("depth", C.c_uint32), ("grid_dim", C.c_uint32 * 3), ("grid_origin", C.c_float * 3),
                 ("grid_inv", C.c_float * 3), ("grid_off", C.c_float * 3)]
+
+
+BOUNCE_CLASSES = 25      # records per leaf in rt_bounce_class_entries_host's table
+BOUNCE_CLASS_FULL = 24   # ... of which this one is the leaf's full record
+
+
+class BounceClassInfo(C.Structure):
+    _fields_ = [("form", C.c_uint32), ("num_records", C.c_uint32), ("num_class_nodes", C.c_uint32),
+                ("first_class_node", C.c_uint32)]
 
 
 class GlibcRand(C.Structure):

@@ -75,7 +75,8 @@ static void free_device(DeviceScene* s) {
     s->bvh_ref_nodes = s->bvh_boxes = s->bvh_ref_pairs = nullptr;
     if (s->leaf_records) (void)hipFree((void*)s->leaf_records);
     if (s->bounce_grid) (void)hipFree((void*)s->bounce_grid);
-    s->leaf_records = s->bounce_grid = nullptr;
+    if (s->class_records) (void)hipFree((void*)s->class_records);
+    s->leaf_records = s->bounce_grid = s->class_records = nullptr;
     if (s->prim_source) (void)hipFree((void*)s->prim_source);
     if (s->flat_source) (void)hipFree((void*)s->flat_source);
     s->prim_source = s->flat_source = nullptr;
@@ -125,6 +126,8 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
         d.leaf_records = p;
         if ((rc = upload(h.bounce_grid, &p, "hipMalloc/hipMemcpy(bounce_grid)"))) goto fail;
         d.bounce_grid = p;
+        if ((rc = upload(h.class_records, &p, "hipMalloc/hipMemcpy(class_records)"))) goto fail;
+        d.class_records = p;
         for (int i = 0; i < 3; i++) {
             d.grid_dim[i] = h.grid_dim[i];
             d.grid_inv[i] = h.grid_inv[i];
@@ -156,7 +159,7 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     d.has_rects = h.has_rects;
     d.device_bytes = (h.nodes.size() + h.nodes48.size() + h.refs.size() + h.prims.size() + h.prims_flat.size() + h.ref_nodes.size() +
                       h.flat_boxes.size() + h.flat_ref_pairs.size() + h.bvh_ref_nodes.size() + h.bvh_boxes.size() + h.bvh_ref_pairs.size() + h.mats.size() +
-                      h.prim_source.size() + h.flat_source.size() + h.leaf_records.size()) * 4 + h.bounce_grid.size() * 2 +
+                      h.prim_source.size() + h.flat_source.size() + h.leaf_records.size() + h.class_records.size()) * 4 + h.bounce_grid.size() * 2 +
                      h.imgs.size() * 4 + h.texels.size();
     *out = s;
     return RT_OK;
@@ -330,6 +333,7 @@ struct LaunchEntry {
     std::vector<rt_material_desc> materials;
     std::vector<ImageKey> images;
     int texel_bytes = 0;  // device bytes per texel of the uploaded block (RT_TUNE_TEXEL_LAYOUT when it was made)
+    int bounce_classes = 0;  // rt_set_bounce_classes when the tables were built
     // shared with the LaunchKernel calls rendering it: an entry evicted or rebuilt by another thread frees
     // its device scene only when the last of them has finished
     std::shared_ptr<rt_scene> scene;
@@ -387,7 +391,7 @@ int reference_scene_for_launch(const void* world, std::shared_ptr<rt_scene>* out
         }
         ent->last_use = ++g_launch_clock;
         const bool geometry = !ent->scene || !same_bytes(ent->hittables, f.hittables) ||
-                              ent->materials.size() != f.materials.size();
+                              ent->materials.size() != f.materials.size() || ent->bounce_classes != g_bounce_classes;
         // the image table of a rebuilt scene takes this thread's texel layout: a block uploaded in the other
         // layout cannot be shared with it (its offsets and strides differ), so a layout change re-uploads
         const int texel_bytes = g_texel_bytes == 4 ? 4 : 3;
@@ -402,6 +406,7 @@ int reference_scene_for_launch(const void* world, std::shared_ptr<rt_scene>* out
             if (r) return r;
             ent->scene = own_scene(fresh, device);
             ent->texel_bytes = texel_bytes;
+            ent->bounce_classes = g_bounce_classes;
         } else if (!same_bytes(ent->materials, f.materials)) {
             r = rt_scene_update_materials(ent->scene.get(), f.materials.data(), (uint32_t)f.materials.size());
             if (r) return r;
@@ -574,8 +579,10 @@ int rt_bounce_entries_host(const rt_scene_desc* desc, float* chain_nodes, float*
         info->grid_off[i] = h.grid_off[i];
     }
     if (chain_nodes) std::copy(h.chain_nodes.begin(), h.chain_nodes.end(), chain_nodes);
-    if (nodes48) std::copy(h.nodes48.begin(), h.nodes48.end(), nodes48);
-    if (refs) std::copy(h.refs.begin(), h.refs.end(), refs);
+    // (the direction classes' nodes, behind these, are rt_bounce_class_entries_host's)
+    const size_t total = (size_t)h.num_nodes + h.num_chain_nodes;
+    if (nodes48) std::copy(h.nodes48.begin(), h.nodes48.begin() + total * 12, nodes48);
+    if (refs) std::copy(h.refs.begin(), h.refs.begin() + total, refs);
     if (records) std::copy(h.leaf_records.begin(), h.leaf_records.end(), records);
     if (grid) std::copy(h.bounce_grid.begin(), h.bounce_grid.end(), grid);
     return RT_OK;
@@ -591,6 +598,64 @@ int rt_bounce_entry_cells(const rt_bounce_entries_info* info, const float* origi
     for (uint32_t i = 0; i < n; i++)
         cells[i] = bounce_cell(origins[3 * (size_t)i], origins[3 * (size_t)i + 1], origins[3 * (size_t)i + 2], info->grid_inv,
                                info->grid_off, dimf, info->grid_dim);
+    return RT_OK;
+}
+
+int rt_set_bounce_classes(int form) {
+    if (form < 0 || form > 2) {
+        set_error("rt_set_bounce_classes: the value must be 0, 1 or 2");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    const int prev = g_bounce_classes;
+    g_bounce_classes = form;
+    return prev;
+}
+
+int rt_bounce_class_entries_host(const rt_scene_desc* desc, int form, uint32_t node_limit, uint32_t* records,
+                                 float* class_nodes48, uint32_t* class_refs, double* regions, const float* origins,
+                                 const float* directions, uint32_t n, uint32_t* classes, rt_bounce_class_info* info) {
+    if (!info) { set_error("rt_bounce_class_entries_host: info is NULL"); return RT_ERR_INVALID_ARGUMENT; }
+    if (form < -1 || form > 2) { set_error("rt_bounce_class_entries_host: form must be -1, 0, 1 or 2"); return RT_ERR_INVALID_ARGUMENT; }
+    if (node_limit > 0x7fffu) { set_error("rt_bounce_class_entries_host: node_limit must be at most 0x7fff"); return RT_ERR_INVALID_ARGUMENT; }
+    if (n && (!directions || !classes)) { set_error("rt_bounce_class_entries_host: NULL directions or classes"); return RT_ERR_INVALID_ARGUMENT; }
+    HostScene h;
+    const int prev_form = g_bounce_classes;
+    const uint32_t prev_limit = g_bounce_class_node_limit;
+    if (form >= 0) g_bounce_classes = form;
+    if (node_limit) g_bounce_class_node_limit = node_limit;
+    int rc = guarded("rt_bounce_class_entries_host", [&]() -> int {
+        std::string err;
+        int r = build_host_scene(desc, &h, &err);
+        if (r) set_error("rt_bounce_class_entries_host: " + err);
+        return r;
+    });
+    g_bounce_classes = prev_form;
+    g_bounce_class_node_limit = prev_limit;
+    if (rc) return rc;
+    std::memset(info, 0, sizeof(*info));
+    info->num_records = (uint32_t)(h.leaf_records.size() / 4);
+    info->form = h.bounce_classes;
+    info->num_class_nodes = h.num_class_nodes;
+    info->first_class_node = h.num_nodes + h.num_chain_nodes;
+    if (h.bounce_classes) {
+        if (records) std::copy(h.class_records.begin(), h.class_records.end(), records);
+        const size_t first = info->first_class_node;
+        if (class_nodes48) std::copy(h.nodes48.begin() + first * 12, h.nodes48.end(), class_nodes48);
+        if (class_refs) std::copy(h.refs.begin() + first, h.refs.end(), class_refs);
+        if (regions) std::copy(h.class_regions.begin(), h.class_regions.end(), regions);
+    }
+    if (n) {
+        if (h.bounce_grid.empty()) {
+            set_error("rt_bounce_class_entries_host: the scene has no bounce-entry table");
+            return RT_ERR_INVALID_ARGUMENT;
+        }
+        const float dims[3] = {(float)h.grid_dim[0], (float)h.grid_dim[1], (float)h.grid_dim[2]};
+        const float zero[3] = {0.0f, 0.0f, 0.0f};
+        for (uint32_t i = 0; i < n; i++)
+            classes[i] = origins ? bounce_class_at(origins + 3 * (size_t)i, directions + 3 * (size_t)i, h.grid_inv, h.grid_off, dims)
+                                 : bounce_class(directions[3 * (size_t)i], directions[3 * (size_t)i + 1],
+                                                directions[3 * (size_t)i + 2], zero[0], zero[1], zero[2]);
+    }
     return RT_OK;
 }
 

@@ -38,6 +38,7 @@
 #include "rt_epilogue.h"
 #include "rt_internal.h"
 #include "rt_scene_device.h"
+#include "rt_bounce_entry.h"
 #include "rt_tile_entry.h"
 
 namespace rt {
@@ -289,7 +290,10 @@ struct KParams {
     const uint16_t* bounce_grid;     // ... per origin-grid cell the index of a record
     float grid_inv[3], grid_off[3];  // ... a ray origin's cell coordinate: fma(o, inv, off) clamped to [0, grid_max]
     float grid_max[3];               // ... dim - 1 per axis
+    float grid_dims[3];              // ... dim per axis (bounce_class: how far outside the grid an origin lies)
     uint32_t grid_nx, grid_ny;       // ... cell = (z * ny + y) * nx + x
+    uint32_t bounce_classes;         // ... bounce_records holds 25 records per leaf, one per direction class of the ray
+                                     // (rt_bounce_entry.h bounce_class; rt_set_bounce_classes), 0 = one record per leaf
 };
 
 constexpr int kStackMax = 64;
@@ -1778,22 +1782,35 @@ __device__ __forceinline__ void v3_start_camera_trace(KParamsC* q, const uint32_
 // its origin (rt_bounce_entry.h): the origin's grid cell names a leaf record, whose entry 0 becomes the lane's postponed
 // leaf, entry 1 its `node` and the rest its stack, the record's last reference at the bottom — the own leaf, then the
 // siblings along its ancestor path from the deepest up, two per chain node.  A "root" record, or a launch without the
-// table, keeps the root.  Per lane: one 2-byte and one 16-byte load and up to six LDS stores.
+// table, keeps the root.  Per lane: one 2-byte and one 16-byte load and up to six LDS stores.  With q->bounce_classes
+// the leaf has one record per direction class of the ray, which leaves out the siblings no ray of the class can reach
+// from the cell's region (rt_bounce_entry.h argues why their primitives' tests cannot accept), and the full one for the
+// rays that argument does not cover; a record may then hold the own leaf alone (`node` = the sentinel pad).
 // Exactness: as for v3_start_camera_trace.  Any leaf's record covers the whole tree with the same conservative box
 // tests (a chain node's boxes are copies of the real nodes'), so every primitive whose test can accept the ray is
 // tested and the geometric closest hit is the root traversal's; ties are flagged in any test order; bvh_clear /
 // ref_trace_wave read the hit record and the reference tables only.  The host has checked every record against the
 // stack's depth entries (scene_build.cpp).
 template <bool WIDE>
-__device__ __forceinline__ void v3_bounce_entry(KParamsC* q, typename RefW<WIDE>::Entry* const stk, const f3 ro, Cursor& c) {
+__device__ __forceinline__ void v3_bounce_entry(KParamsC* q, typename RefW<WIDE>::Entry* const stk, const f3 ro, const f3 rd,
+                                                Cursor& c) {
     if constexpr (!WIDE) {
         const uint4* const recs = q->bounce_records;
         if (!recs) return;  // (launch-uniform)
-        const float fx = fminf(fmaxf(__builtin_fmaf(ro.x, q->grid_inv[0], q->grid_off[0]), 0.0f), q->grid_max[0]);
-        const float fy = fminf(fmaxf(__builtin_fmaf(ro.y, q->grid_inv[1], q->grid_off[1]), 0.0f), q->grid_max[1]);
-        const float fz = fminf(fmaxf(__builtin_fmaf(ro.z, q->grid_inv[2], q->grid_off[2]), 0.0f), q->grid_max[2]);
+        const float ux = __builtin_fmaf(ro.x, q->grid_inv[0], q->grid_off[0]);
+        const float uy = __builtin_fmaf(ro.y, q->grid_inv[1], q->grid_off[1]);
+        const float uz = __builtin_fmaf(ro.z, q->grid_inv[2], q->grid_off[2]);
+        const float fx = fminf(fmaxf(ux, 0.0f), q->grid_max[0]);
+        const float fy = fminf(fmaxf(uy, 0.0f), q->grid_max[1]);
+        const float fz = fminf(fmaxf(uz, 0.0f), q->grid_max[2]);
         const uint32_t cell = ((uint32_t)fz * q->grid_ny + (uint32_t)fy) * q->grid_nx + (uint32_t)fx;
-        const uint4 r = recs[q->bounce_grid[cell]];
+        uint32_t rec = q->bounce_grid[cell];
+        // (launch-uniform) the record of the ray's direction class: the siblings it can reach from the cell's region
+        if (q->bounce_classes)
+            rec = rec * kBounceClasses + bounce_class(rd.x, rd.y, rd.z, ux - fminf(fmaxf(ux, 0.0f), q->grid_dims[0]),
+                                                      uy - fminf(fmaxf(uy, 0.0f), q->grid_dims[1]),
+                                                      uz - fminf(fmaxf(uz, 0.0f), q->grid_dims[2]));
+        const uint4 r = recs[rec];
         const uint32_t e0 = r.x & 0xffffu;
         if (e0 != kTileEntryRoot) {
             c.leaf = (int)e0;
@@ -2596,7 +2613,7 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
                 v3_park<COMPACT, false>(park, rng, col, att, sample, depth, rays);
             }
             // (behind the park: the path state is out of the registers when the record arrives)
-            if (bounce) v3_bounce_entry<WIDE>(kparams_reload(), stk, ro, c);
+            if (bounce) v3_bounce_entry<WIDE>(kparams_reload(), stk, ro, rd, c);
             // (RT_REPLAY_SAME_PASS: the lanes shade() returned SHADE_REPLAY for replay now, every lane active, and shade)
             if (!RT_REPLAY_SAME_PASS || __ballot(c.mode == MODE_REPLAY) == 0u) break;
             bvh_replay_wave(kparams_reload(), prims, c, ro, rd, cnt, COUNT_TESTS);
@@ -5720,12 +5737,14 @@ int bind_tile_entries(dev::KParams& P, const int kernel, const DeviceScene& S, h
 // v3 on a scene with the bounce-entry tables (rt_bounce_entry.h): bounce rays start at a leaf near their origin
 void bind_bounce_entries(dev::KParams& P, const int kernel, const DeviceScene& S) {
     if (kernel != 3 || S.wide_refs || !g_bounce_entries || !S.leaf_records || !S.bounce_grid) return;
-    P.bounce_records = (const uint4*)S.leaf_records;
+    P.bounce_classes = g_bounce_classes && S.class_records ? 1u : 0u;
+    P.bounce_records = (const uint4*)(P.bounce_classes ? S.class_records : S.leaf_records);
     P.bounce_grid = (const uint16_t*)S.bounce_grid;
     for (int i = 0; i < 3; i++) {
         P.grid_inv[i] = S.grid_inv[i];
         P.grid_off[i] = S.grid_off[i];
         P.grid_max[i] = (float)(S.grid_dim[i] - 1u);
+        P.grid_dims[i] = (float)S.grid_dim[i];
     }
     P.grid_nx = S.grid_dim[0];
     P.grid_ny = S.grid_dim[1];

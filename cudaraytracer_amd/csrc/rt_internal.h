@@ -98,7 +98,17 @@ struct HostScene {
     float grid_origin[3] = {0.0f, 0.0f, 0.0f};
     float grid_inv[3] = {0.0f, 0.0f, 0.0f};  // cells per unit length
     float grid_off[3] = {0.0f, 0.0f, 0.0f};  // -origin * inv: the cell coordinate is fma(o, inv, off)
+    // Direction classes of the bounce entries (rt_bounce_entry.h), built when g_bounce_classes asks for them
+    uint32_t bounce_classes = 0;          // the form that was built: 0 = none, 1 = existing pairs, 2 = re-paired
+    uint32_t num_class_nodes = 0;         // form 2: chain nodes behind the num_chain_nodes ones in nodes48 / refs
+    std::vector<uint32_t> class_records;  // 4 words per (leaf record, class): record r's class c at (r * 25 + c) * 4
+    std::vector<double> class_regions;    // per leaf record its region: lo.xyz, hi.xyz (lo > hi: no cell names it)
 };
+
+// rt_set_bounce_classes: the form build_host_scene builds (thread-local), and the node count at which form 2 falls
+// back to form 1 (real + chain + class nodes must stay below it; lowered by rt_bounce_class_entries_host for tests).
+extern thread_local int g_bounce_classes;
+extern thread_local uint32_t g_bounce_class_node_limit;
 
 // Validate + build (host only).  Returns RT_OK or an rt_status, with `err` set.  with_texels = false computes
 // the image table but leaves `texels` empty (a rebuild that reuses an uploaded texel block).

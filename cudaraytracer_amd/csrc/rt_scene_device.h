@@ -26,6 +26,7 @@ struct DeviceScene {
     const void* flat_source = nullptr;  // ... per prims_flat record, or NULL (rt_gbuffer's prim_id)
     const void* leaf_records = nullptr;  // bounce entries (rt_bounce_entry.h): uint4 per leaf, or NULL = no table
     const void* bounce_grid = nullptr;   // ... uint16 per grid cell: the index of a leaf record
+    const void* class_records = nullptr; // ... uint4 per (leaf record, direction class), or NULL (rt_set_bounce_classes)
     uint32_t grid_dim[3] = {0u, 0u, 0u};
     float grid_inv[3] = {0.0f, 0.0f, 0.0f}, grid_off[3] = {0.0f, 0.0f, 0.0f};
     const void* mats = nullptr;    // float4 × 3 per material

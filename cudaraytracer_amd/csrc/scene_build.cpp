@@ -8,6 +8,7 @@
 // primitive tests alone decide the hit, boxes only cull (see rt_internal.h).
 #include <algorithm>
 #include <limits>
+#include <map>
 #include <functional>
 #include <array>
 #include <cmath>
@@ -17,7 +18,17 @@
 #include "rt_bounce_entry.h"
 #include "rt_internal.h"
 
+// rt_set_bounce_classes' default: 2, the re-paired form (profiles/r14a_ab_bounce_classes.txt); an
+// A/B build sets another
+#ifndef RT_BOUNCE_CLASSES_DEFAULT
+#define RT_BOUNCE_CLASSES_DEFAULT 2
+#endif
+
 namespace rt {
+
+thread_local int g_bounce_classes = RT_BOUNCE_CLASSES_DEFAULT;
+thread_local uint32_t g_bounce_class_node_limit = 0x7fffu;
+
 namespace {
 
 struct Box {
@@ -419,12 +430,153 @@ void build_bounce_entries(const Builder& B, HostScene* out) {
                 out->bounce_grid[((size_t)z * dim[1] + y) * dim[0] + x] = (uint16_t)best;
             }
 
-    out->num_chain_nodes = (uint32_t)chain.size();
-    out->chain_nodes.resize(chain.size() * 16);
+    // Direction classes (rt_bounce_entry.h): per record and class the siblings a ray of the class can reach from the
+    // record's region; form 2 appends its pairs to `chain`, behind the num_chain nodes of the full records
+    const size_t num_chain = chain.size();
+    bool flat_axis = false;
+    for (int i = 0; i < 3; i++) flat_axis = flat_axis || !(out->grid_inv[i] > 0.0f);
+    if (g_bounce_classes != 0 && !flat_axis) {
+        const size_t R = records.size();
+        std::vector<double>& reg = out->class_regions;
+        reg.resize(R * 6);
+        for (size_t r = 0; r < R; r++)
+            for (int i = 0; i < 3; i++) { reg[6 * r + i] = INFINITY; reg[6 * r + 3 + i] = -INFINITY; }
+        for (uint32_t z = 0; z < dim[2]; z++)
+            for (uint32_t y = 0; y < dim[1]; y++)
+                for (uint32_t x = 0; x < dim[0]; x++) {
+                    const uint32_t cell[3] = {x, y, z};
+                    double* q = reg.data() + 6 * (size_t)out->bounce_grid[((size_t)z * dim[1] + y) * dim[0] + x];
+                    for (int i = 0; i < 3; i++) {
+                        // the origins whose exact o * inv + off lies in [cell, cell + 1); a border cell one cell further
+                        const double inv = (double)out->grid_inv[i], off = (double)out->grid_off[i];
+                        const double lo = ((cell[i] == 0 ? -1.0 : (double)cell[i]) - off) / inv;
+                        const double hi = ((cell[i] + 1u == dim[i] ? (double)dim[i] + 1.0 : (double)cell[i] + 1.0) - off) / inv;
+                        q[i] = std::min(q[i], lo);
+                        q[3 + i] = std::max(q[3 + i], hi);
+                    }
+                }
+        // whether a subtree holds a spanning primitive (every primitive counts as one where all of them span)
+        std::vector<signed char> span_node(N, -1);
+        std::function<bool(int)> spans = [&](const int ref) -> bool {
+            if (ref < 0) {
+                if (!any) return true;
+                const uint32_t r = ~(uint32_t)ref, first = r >> 2, count = (r & 3u) + 1u;
+                for (uint32_t i = first; i < first + count; i++)
+                    if (spanning(B.prims[B.order[i]])) return true;
+                return false;
+            }
+            if (span_node[ref] < 0) {
+                const bool a = spans(B.nodes[ref].child[0]), b = spans(B.nodes[ref].child[1]);
+                span_node[ref] = a || b;
+            }
+            return span_node[ref] != 0;
+        };
+        const auto reachable = [](const double* Rg, const Box& S, const uint32_t cls) -> bool {
+            const uint32_t k = cls >> 3;
+            double D = 0.0, A = 0.0;
+            for (int j = 0; j < 3; j++) {
+                const double slo = (double)S.lo[j], shi = (double)S.hi[j], rlo = Rg[j], rhi = Rg[3 + j];
+                D += (rhi > shi ? rhi : shi) - (rlo < slo ? rlo : slo);
+                double a = rlo < 0.0 ? -rlo : rlo;
+                const double b = rhi < 0.0 ? -rhi : rhi, c = slo < 0.0 ? -slo : slo, d = shi < 0.0 ? -shi : shi;
+                a = a > b ? a : b;
+                a = a > c ? a : c;
+                A += a > d ? a : d;
+            }
+            const double m = 0x1p-8 * D + 0x1p-18 * A;
+            if (!(m - m == 0.0)) return true;  // (a box that is not finite stays)
+            const bool neg_k = (cls >> k & 1u) != 0;
+            const double s = neg_k ? Rg[3 + k] - (double)S.lo[k] : (double)S.hi[k] - Rg[k];
+            if (s < -m) return false;
+            for (uint32_t j = 0; j < 3; j++) {
+                if (j == k) continue;
+                const bool neg = (cls >> j & 1u) != 0;
+                const double lo = neg ? Rg[j] - s - m : Rg[j], hi = neg ? Rg[3 + j] : Rg[3 + j] + s + m;
+                if ((double)S.hi[j] < lo - m || (double)S.lo[j] > hi + m) return false;
+            }
+            return true;
+        };
+        std::vector<uint32_t>& cr = out->class_records;
+        for (uint32_t form = (uint32_t)g_bounce_classes;; form = 1) {
+            chain.resize(num_chain);
+            cr.assign(R * kBounceClasses * 4, 0u);
+            std::map<std::pair<int, int>, int> pair_id;
+            for (size_t i = 0; i < num_chain; i++) pair_id[{chain[i].child[0], chain[i].child[1]}] = (int)(N + i);
+            for (size_t l = 0; l < R; l++) {
+                const Leaf& L = leaves[l];
+                const size_t a = L.path.size();
+                const double* Rg = reg.data() + 6 * l;
+                const bool whole = records[l][0] == kTileEntryRoot || !(Rg[0] <= Rg[3]);
+                const auto sib_ref = [&](const size_t i) { return B.nodes[L.path[i].node].child[1 - L.path[i].side]; };
+                const auto sib_box = [&](const size_t i) -> const Box& { return B.nodes[L.path[i].node].box[1 - L.path[i].side]; };
+                for (uint32_t cls = 0; cls < kBounceClasses; cls++) {
+                    std::array<uint32_t, kTileEntryMax> e = records[l];
+                    if (!whole && cls != kBounceClassFull) {
+                        std::vector<char> reach(a);
+                        for (size_t i = 0; i < a; i++) reach[i] = spans(sib_ref(i)) || reachable(Rg, sib_box(i), cls);
+                        std::vector<int> refs;  // behind the own leaf, from the deepest up
+                        if (form == 1) {
+                            if ((a & 1u) && reach[a - 1]) refs.push_back(sib_ref(a - 1));
+                            for (size_t k = a / 2; k >= 1; k--)
+                                if (reach[2 * k - 1] || reach[2 * k - 2])
+                                    refs.push_back(chain_of[(size_t)L.path[2 * k - 1].node * 2 + (size_t)L.path[2 * k - 1].side]);
+                        } else {
+                            std::vector<size_t> kept;  // from the root
+                            for (size_t i = 0; i < a; i++)
+                                if (reach[i]) kept.push_back(i);
+                            if (kept.size() & 1u) refs.push_back(sib_ref(kept.back()));
+                            for (size_t k = kept.size() / 2; k >= 1; k--) {
+                                const size_t lo = kept[2 * k - 1], up = kept[2 * k - 2];  // the deeper one is child 0
+                                int& id = pair_id[{sib_ref(lo), sib_ref(up)}];
+                                if (id == 0) {  // (no chain node has index 0: N >= 1)
+                                    id = (int)(N + chain.size());
+                                    Builder::Node c;
+                                    c.child[0] = sib_ref(lo);
+                                    c.box[0] = sib_box(lo);
+                                    c.child[1] = sib_ref(up);
+                                    c.box[1] = sib_box(up);
+                                    chain.push_back(c);
+                                }
+                                refs.push_back(id);
+                            }
+                        }
+                        // the stack simulation of the full records
+                        const size_t m = refs.size();
+                        bool fits = m <= kBounceChainMax && (m == 0 || m - 1 <= out->depth);
+                        for (size_t j = 0; j < m && fits; j++) {
+                            const uint32_t h = (uint32_t)(m - 1 - j);
+                            uint32_t top = 0;
+                            if (refs[j] >= (int)N) {
+                                const Builder::Node& c = chain[(size_t)refs[j] - N];
+                                top = h + 1u + std::max(ref_height(c.child[0]), ref_height(c.child[1]));
+                            } else if (refs[j] >= 0) {
+                                top = h + height[refs[j]];
+                            }
+                            fits = top <= out->depth;
+                        }
+                        if (fits) {
+                            e.fill(kTileEntryNone);
+                            e[0] = (uint32_t)L.ref & 0xffffu;
+                            for (size_t j = 0; j < m; j++) e[1 + j] = (uint32_t)refs[j] & 0xffffu;
+                        }
+                    }
+                    uint32_t* w = cr.data() + (l * kBounceClasses + cls) * 4;
+                    for (int i = 0; i < 4; i++) w[i] = e[2 * i] | (e[2 * i + 1] << 16);
+                }
+            }
+            if (form == 2 && N + chain.size() >= g_bounce_class_node_limit) continue;  // fall back to form 1
+            out->bounce_classes = form;
+            break;
+        }
+        out->num_class_nodes = (uint32_t)(chain.size() - num_chain);
+    }
+
+    out->num_chain_nodes = (uint32_t)num_chain;
+    out->chain_nodes.resize(num_chain * 16);
     out->nodes48.resize((size_t)(N + chain.size()) * 12);
     out->refs.resize((size_t)N + chain.size());
     for (size_t i = 0; i < chain.size(); i++) {
-        pack_node16(chain[i], out->chain_nodes.data() + i * 16);
+        if (i < num_chain) pack_node16(chain[i], out->chain_nodes.data() + i * 16);
         pack_node48(chain[i], false, out->nodes48.data() + (N + i) * 12);
         out->refs[N + i] = ((uint32_t)chain[i].child[0] & 0xffffu) | ((uint32_t)chain[i].child[1] << 16);
     }

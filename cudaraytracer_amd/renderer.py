@@ -174,6 +174,16 @@ def set_tile_occlusion(on: bool) -> bool:
     return bool(prev)
 
 
+def set_bounce_classes(form: int) -> int:
+    """rt_set_bounce_classes for the calling thread: the direction-class records of the v3 kernels' bounce entries that
+    scenes created afterwards carry (0 = none, 1 = the existing chain nodes, 2 = re-paired; same pixels in every form).
+    Returns the previous value."""
+    prev = lib().rt_set_bounce_classes(int(form))
+    if prev < 0:
+        check(prev, "rt_set_bounce_classes")
+    return prev
+
+
 def camera_rays(inputs: abi.InputStruct, width: int, height: int, pixels=None, jitter=(0.5, 0.5), sample: int = 0,
                 seed: int = 1984, frame: int = 0, tiling: abi.Tiling | None = None, device=None):
     """The library's own camera rays as a ray batch (rt_camera_rays), asynchronous on torch's current stream: the rays

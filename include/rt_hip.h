@@ -187,7 +187,8 @@ const char* rt_version(void);
  * 13: rt_temporal_moments, rt_denoise_variance, rt_denoise_variance_scratch_bytes.  14: rt_query_rays; rt_gbuffer and
  * rt_trace_rays take scenes with 32-bit BVH references; later additions that change no structure layout, counter
  * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells,
- * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays, rt_camera_rays, rt_radiance_rays (a caller asks the
+ * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays, rt_camera_rays, rt_radiance_rays,
+ * rt_set_bounce_classes, rt_bounce_class_entries_host (a caller asks the
  * library for them by name). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
@@ -986,6 +987,32 @@ int rt_bounce_entries_host(const rt_scene_desc* desc, float* chain_nodes, float*
                            uint32_t* records, uint16_t* grid, rt_bounce_entries_info* info);
 /* The grid cells of n origins (x, y, z each) as the kernel computes them. */
 int rt_bounce_entry_cells(const rt_bounce_entries_info* info, const float* origins, uint32_t n, uint32_t* cells);
+
+/* Direction classes of the bounce entries (csrc/rt_bounce_entry.h): per leaf record 25 records of the same form, one
+ * per class of ray direction (the axis of the largest |d|, its sign, the other two signs: 24) that list only the
+ * siblings a ray of the class can reach from the grid cells that name the record, and the full record as class 24 for
+ * the rays that argument does not cover.  form 0 = off (the full records), 1 = the full records' chain nodes, kept
+ * where either child can be reached, 2 = the reachable siblings paired anew as further chain nodes (falls back to 1
+ * where real + chain nodes would reach 0x7fff).  The form holds for the scenes a thread creates afterwards (and the
+ * tables LaunchKernel builds); a render uses a scene's class records unless the thread's value is 0 or
+ * rt_set_bounce_entries is.  Same pixels, RNG states and ray counts in every form.  Thread-local; returns the previous
+ * value, or RT_ERR_INVALID_ARGUMENT for a value other than 0, 1 or 2. */
+int rt_set_bounce_classes(int form);
+
+/* Those tables, built on the host only (for inspection/tests).  form: 0..2, or -1 = the thread's rt_set_bounce_classes
+ * value; node_limit: real + chain + class nodes must stay below it (0 = 0x7fff).  info->form is the form that was
+ * built (0: none; 1 for a form 2 that fell back).  Size query with NULL arrays.  records: 4 words per (leaf record,
+ * class), record r's class c at (r * 25 + c) * 4, class 24 being rt_bounce_entries_host's record r; class_nodes48 /
+ * class_refs: 12 floats / one word per class node, which follow rt_bounce_entries_host's nodes from index
+ * first_class_node; regions: per leaf record lo.xyz, hi.xyz as binary64 (lo > hi: no grid cell names the record).
+ * classes: the class of each of n rays as the kernel computes it, from directions (x, y, z each) and origins
+ * (origins = NULL: the direction's class alone). */
+typedef struct rt_bounce_class_info {
+    uint32_t form, num_records, num_class_nodes, first_class_node;
+} rt_bounce_class_info;
+int rt_bounce_class_entries_host(const rt_scene_desc* desc, int form, uint32_t node_limit, uint32_t* records,
+                                 float* class_nodes48, uint32_t* class_refs, double* regions, const float* origins,
+                                 const float* directions, uint32_t n, uint32_t* classes, rt_bounce_class_info* info);
 
 /* glibc random_r TYPE_3 restatement: rand() sequence after srand(seed) (RND macro, Math.cuh:12). */
 typedef struct rt_glibc_rand { int32_t r[34]; uint32_t idx; } rt_glibc_rand;

@@ -80,6 +80,9 @@ EXPORTED = [
     "rt_bounce_entry_cells",
     "rt_set_bounce_classes",
     "rt_bounce_class_entries_host",
+    "rt_adaptive_select",
+    "rt_adaptive_select_scratch_bytes",
+    "rt_adaptive_samples",
 ]
 
 _lib = None
@@ -173,6 +176,11 @@ def _declare(lib: C.CDLL) -> None:
         lib.rt_bounce_class_entries_host.argtypes = [P(abi.SceneDesc), C.c_int, C.c_uint32, P(C.c_uint32), P(C.c_float),
                                                      P(C.c_uint32), P(C.c_double), P(C.c_float), P(C.c_float), C.c_uint32,
                                                      P(C.c_uint32), P(abi.BounceClassInfo)]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_adaptive_select"):  # (an A/B build of an older revision lacks them)
+        lib.rt_adaptive_select.argtypes = [P(abi.AdaptiveSelectArgs), vp]
+        lib.rt_adaptive_select_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
+        lib.rt_adaptive_select_scratch_bytes.restype = C.c_uint64
+        lib.rt_adaptive_samples.argtypes = [vp, P(abi.AdaptiveSamplesArgs), vp]
     lib.LaunchKernel.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, abi.InputStruct]
     lib.LaunchKernel.restype = None
     lib.LaunchRandInit.argtypes = [vp]

@@ -31,8 +31,8 @@ RT_TEMPORAL_RESET = 1 << 1
 # 11: RT_TUNE_CAMERA_RESOLVE; 12: RT_TUNE_PATH_END_STEP; 13: rt_temporal_moments, rt_denoise_variance,
 # rt_denoise_variance_scratch_bytes; 14: rt_query_rays, 32-bit references in rt_gbuffer and rt_trace_rays
 # (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells, rt_occluded_rays, rt_camera_rays,
-# rt_radiance_rays, rt_set_bounce_classes and rt_bounce_class_entries_host were added without a new number: no layout
-# changed)
+# rt_radiance_rays, rt_set_bounce_classes, rt_bounce_class_entries_host, rt_adaptive_select,
+# rt_adaptive_select_scratch_bytes and rt_adaptive_samples were added without a new number: no layout changed)
 ABI_VERSION = 14
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
@@ -268,6 +268,60 @@ class RadianceArgs(C.Structure):
         ("background_start", F3),
         ("background_end", F3),
         ("reserved", C.c_uint32 * 3),
+    ]
+
+
+class AdaptiveSelectArgs(C.Structure):
+    """rt_adaptive_select_args, 120 bytes."""
+
+    _fields_ = [
+        ("history", C.c_void_p),
+        ("moments", C.c_void_p),
+        ("prim_id", C.c_void_p),
+        ("pixels", C.c_void_p),
+        ("samples", C.c_void_p),
+        ("count", C.c_void_p),
+        ("scratch", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("capacity", C.c_uint32),
+        ("max_samples", C.c_uint32),
+        ("min_history", C.c_uint32),
+        ("tau", C.c_float),
+        ("lum_floor", C.c_float),
+        ("pixels_per_lane", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+        ("tiling", Tiling),
+    ]
+
+
+class AdaptiveSamplesArgs(C.Structure):
+    """rt_adaptive_samples_args, 192 bytes."""
+
+    _fields_ = [
+        ("pixels", C.c_void_p),
+        ("samples", C.c_void_p),
+        ("count", C.c_void_p),
+        ("history", C.c_void_p),
+        ("moments", C.c_void_p),
+        ("accum", C.c_void_p),
+        ("counters", C.c_void_p),
+        ("capacity", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("samples_per_pixel", C.c_uint32),
+        ("max_samples", C.c_uint32),
+        ("sample_base", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("max_history", C.c_uint32),
+        ("rays_per_lane", C.c_uint32),
+        ("count_tests", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("rng_frame", C.c_uint32),
+        ("rng_seed", C.c_uint64),
+        ("inputs", InputStruct),
+        ("reserved", C.c_uint32 * 2),
     ]
 
 

@@ -4265,6 +4265,156 @@ __global__ __launch_bounds__(64, 4) void radiance_rays_kernel(const RadiancePara
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The extra samples of a pixel list, traced and merged (rt_adaptive_samples): radiance_rays_kernel's schedule with list
+// entries as work items.  A lane owns entry i — pixel pixels[i], k_i paths — from its first camera ray to its merge.
+// Path j is the pixel's sample s = sample_base + j: camera_ray draws the jitter from block 0 of the sample's window
+// (lane_camera and camera_ray as the render kernels call them, so no ray batch exists in memory and every path has its
+// own sub-pixel position), and the bounce loop goes on from block 1, which is rt_radiance_rays' path.  The pixel's
+// history and moments are loaded when the entry starts, blended once per path in sample order (step 5 of rt_temporal /
+// rt_temporal_moments for a resting camera) and stored when it ends; the accumulation plane takes the entry's
+// fixed-point sum.  The number of entries is read from the device (count[0], rt_adaptive_select's), so the host launches
+// for the list's capacity and a wave whose range lies beyond the count leaves at once.  Every pixel is listed at most
+// once and is read and written by its own lane: the result does not depend on the schedule.
+// ---------------------------------------------------------------------------------------------------
+struct AdaptiveParams {
+    KParams K;
+    const uint32_t* pixels;
+    const uint32_t* samples;
+    const uint32_t* count;
+    float4* history;
+    float2* moments;
+    float4* accum;
+    uint32_t capacity, per_wave;
+    uint32_t spp, max_samples, sample_base;
+    float max_history;
+};
+static_assert(offsetof(AdaptiveParams, K) == 0, "philox_block and kparams_reload read the kernel arguments as a KParams");
+
+template <bool COUNT_TESTS, bool WIDE>
+__global__ __launch_bounds__(64, 4) void adaptive_samples_kernel(const AdaptiveParams Q) {
+    using Entry = typename RefW<WIDE>::Entry;
+    const KParams* P = &Q.K;
+    extern __shared__ float4 lds[];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t entries = Q.count ? min(Q.count[0], Q.capacity) : Q.capacity;  // (wave-uniform)
+    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers capacity: base < capacity)
+    if (base >= entries) return;
+    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
+    const __amdgpu_buffer_rsrc_t nrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+    stk[0] = (Entry)RefW<WIDE>::kSentinel;
+    stk[64] = (Entry)RefW<WIDE>::kSentinel;
+    const uint32_t count = min(entries - base, Q.per_wave);  // entries of this wave's range
+    const uint32_t frame_pixels = P->width * P->height;      // (below 2^31: checked on the host)
+    Counts cnt{0, 0, 0, 0, 0, 0, 0};
+    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+    uint32_t nrays = 0u, npaths = 0u;
+    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
+    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the entry's sample sums, 2^-12 units (the accumulation plane's)
+    float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the pixel's history and moments while the lane owns it
+    float2 mo = make_float2(0.0f, 0.0f);
+    uint32_t pixel = 0u, paths = 0u, sample = 0u, depth = 0u;
+    RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
+    const bool rtl = P->rius_rtl != 0;
+    // the pixel's path of sample sample_base + `sample` starts: its own camera ray, then block 1 of the sample's window
+    const auto begin_path = [&]() {
+        KParamsC* const q = kparams_reload();
+        const uint32_t g = pixel / q->width, x = pixel - g * q->width;
+        camera_ray(q, lane_camera(q, x, g), rng, ro, rd, Q.sample_base + sample);
+        att = mk(1.0f, 1.0f, 1.0f);
+        depth = 0u;
+        npaths++;
+        v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+    };
+    // a path ended with these 2^-12 units per channel: one more frame's blend, and the entry's sum
+    const auto merge = [&](const uint32_t u0, const uint32_t u1, const uint32_t u2) {
+        q0 = sat_add(q0, u0);
+        q1 = sat_add(q1, u1);
+        q2 = sat_add(q2, u2);
+        if (Q.history) {
+            const f3 cs = mk((float)u0 * (1.0f / 4096.0f), (float)u1 * (1.0f / 4096.0f), (float)u2 * (1.0f / 4096.0f));
+            const float N = fminf(h.w + 1.0f, Q.max_history);
+            const float alpha = 1.0f / N;
+            h = make_float4(h.x + alpha * (cs.x - h.x), h.y + alpha * (cs.y - h.y), h.z + alpha * (cs.z - h.z), N);
+            const float l = (0.2126f * cs.x + 0.7152f * cs.y) + 0.0722f * cs.z;
+            mo = make_float2(mo.x + alpha * (l - mo.x), mo.y + alpha * (l * l - mo.y));
+        }
+    };
+    const auto store = [&]() {
+        if (Q.history) Q.history[pixel] = h;
+        if (Q.moments) Q.moments[pixel] = mo;
+        if (Q.accum) {
+            const float4 a = Q.accum[pixel];
+            const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
+            Q.accum[pixel] = make_float4(a.x + s.x, a.y + s.y, a.z + s.z, a.w + (float)paths);
+        }
+        c.mode = MODE_NEED;
+    };
+    const auto start = [&](uint32_t i) {
+        pixel = Q.pixels[i];
+        paths = min(Q.samples ? Q.samples[i] : Q.spp, Q.max_samples);
+        if (pixel >= frame_pixels || paths == 0u) {  // not an entry: nothing is read or written
+            c.mode = MODE_NEED;
+            return;
+        }
+        rng.pix = pixel;
+        q0 = q1 = q2 = 0u;
+        sample = 0u;
+        if (Q.history) h = Q.history[pixel];
+        if (Q.moments) mo = Q.moments[pixel];
+        if (P->max_depth != 0u) {
+            begin_path();
+        } else {  // exceeded recursion at once (Kernel.cu:79): every sample is 0, nothing is traced
+            npaths += paths;
+            for (uint32_t j = 0; j < paths; j++) merge(0u, 0u, 0u);
+            c.mode = MODE_ENDED;
+        }
+    };
+    if (lane < count) start(base + lane);
+    uint32_t taken = 64u;  // wave-uniform: entries of the wave's range handed out so far
+    while (__ballot(c.mode != MODE_DONE) != 0) {
+        if (c.mode == MODE_TRAV) {
+            uint32_t thr = P->regen_threshold;
+            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c, cnt, 64u,
+                                                                P->leaf_break);
+        }
+        if (c.mode == MODE_SHADE) {
+            if (COUNT_TESTS) cnt.wshade += wave_leader();
+            KParamsC* const q = kparams_reload();
+            f3 contrib;
+            const int res = shade<true, false, false>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att, rng, rtl,
+                                                      contrib);
+            bool ended = res == SHADE_ENDED;
+            if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
+                ended = true;
+                contrib = mk(0.0f, 0.0f, 0.0f);
+            }
+            if (!ended) {
+                v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+            } else {
+                merge(quant12(contrib.x), quant12(contrib.y), quant12(contrib.z));
+                if (++sample < paths) begin_path();
+                else c.mode = MODE_ENDED;
+            }
+        }
+        if (c.mode == MODE_ENDED) store();
+        const uint64_t needm = __ballot(c.mode == MODE_NEED);
+        if (needm != 0) {
+            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
+            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088 beyond the skipped entries' turns)
+            if (c.mode == MODE_NEED) {
+                if (k < count) start(base + k);
+                else c.mode = MODE_DONE;
+            }
+        }
+    }
+    cnt.rays = nrays;
+    cnt.primary = npaths;
+    flush_counts<COUNT_TESTS>(*P, cnt);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The camera rays of the render kernels as a ray batch (rt_camera_rays): one lane per ray, camera_ray / camera_ray_at
 // and lane_camera themselves.  rays[2i] = (origin, kTmin), rays[2i + 1] = (direction, FLT_MAX): color()'s range.  The
 // params begin with a KParams (camera_ray's Philox draw reads key and frame through the kernel-argument pointer).
@@ -5398,6 +5548,79 @@ int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* a, rt_stream
                                     : (a->count_tests ? dev::radiance_rays_kernel<true, false> : dev::radiance_rays_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
     return hip_check(hipGetLastError(), "rt_radiance_rays: kernel launch", RT_ERR_LAUNCH);
+}
+
+int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a, rt_stream stream) {
+    // (every argument check runs before the first device call and before the scene is read)
+    const auto bad = [](const std::string& what) {
+        set_error("rt_adaptive_samples: " + what);
+        return (int)RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!a) return bad("NULL args");
+    if ((a->flags & ~(uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT) != 0) return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT");
+    if (a->reserved[0] != 0 || a->reserved[1] != 0) return bad("reserved must be 0");
+    if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
+    if (a->count_tests > 1u) return bad("count_tests must be 0 or 1");
+    if (a->count_tests && !a->counters) return bad("count_tests without counters");
+    if (!a->history && !a->accum) return bad(a->moments ? "moments without history" : "no target plane (history or accum)");
+    if (a->moments && !a->history) return bad("moments without history");
+    if (a->max_samples < 1u || a->max_samples > 16u) return bad("max_samples must be 1..16");
+    if (!a->samples && a->samples_per_pixel == 0u) return bad("samples_per_pixel must be at least 1 without samples");
+    if ((uint64_t)a->sample_base + a->max_samples > RT_PHILOX_MAX_SPP)
+        return bad("sample_base + max_samples above RT_PHILOX_MAX_SPP (16384)");
+    if (a->max_history < 1u || a->max_history > 4096u) return bad("max_history must be 1..4096");
+    const uint64_t n = (uint64_t)a->width * a->height, cap = a->capacity;
+    if (n > 0x7fffffffull) return bad("frame too large (width * height)");
+    if (cap == 0) return RT_OK;  // nothing to trace
+    if (!a->pixels) return bad("NULL pixels");
+    if (n == 0) return bad("an empty frame (width or height 0) with capacity > 0");
+    const char* const names[7] = {"pixels", "samples", "count", "counters", "history", "moments", "accum"};
+    const void* const bufs[7] = {a->pixels, a->samples, a->count, a->counters, a->history, a->moments, a->accum};
+    const uint64_t bytes[7] = {cap * 4u, cap * 4u, 4u, (uint64_t)RT_COUNTERS_WORDS * 8u, n * 16u, n * 8u, n * 16u};
+    for (int i = 0; i < 7; i++)
+        for (int j = 0; j < i; j++)
+            if (overlaps(bufs[i], bytes[i], bufs[j], bytes[j])) return bad(std::string(names[i]) + " overlaps " + names[j]);
+    if (!scene) return bad("NULL scene");
+    const DeviceScene& S = scene->dev;
+    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
+    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_adaptive_samples: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    dev::AdaptiveParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    dev::KParams& P = Q.K;
+    fill_scene_tables(P, S);
+    P.width = a->width;  // (global indices: one band of the whole frame, as rt_camera_rays' sparse form)
+    P.height = a->height;
+    P.band_rows = 1u;
+    P.num_ranks = 1u;
+    fill_camera(P, a->inputs, a->width, a->height);  // (the sky too)
+    P.counters = (unsigned long long*)a->counters;
+    P.regen_threshold = (uint32_t)g_regen_threshold;
+    P.regen_live_frac = (uint32_t)g_regen_live_frac;
+    P.leaf_break = (uint32_t)g_leaf_break;
+    P.max_depth = a->max_depth;
+    P.rius_rtl = (a->flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
+    P.rng_key_lo = (uint32_t)a->rng_seed;
+    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
+    P.rng_frame = a->rng_frame;
+    Q.pixels = a->pixels;
+    Q.samples = a->samples;
+    Q.count = a->count;
+    Q.history = (float4*)a->history;
+    Q.moments = (float2*)a->moments;
+    Q.accum = (float4*)a->accum;
+    Q.capacity = a->capacity;
+    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->capacity));
+    Q.spp = a->samples_per_pixel;
+    Q.max_samples = a->max_samples;
+    Q.sample_base = a->sample_base;
+    Q.max_history = (float)a->max_history;
+    const uint32_t grid = (uint32_t)((cap + Q.per_wave - 1) / Q.per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    const auto kernel = S.wide_refs ? (a->count_tests ? dev::adaptive_samples_kernel<true, true> : dev::adaptive_samples_kernel<false, true>)
+                                    : (a->count_tests ? dev::adaptive_samples_kernel<true, false> : dev::adaptive_samples_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
+    return hip_check(hipGetLastError(), "rt_adaptive_samples: kernel launch", RT_ERR_LAUNCH);
 }
 
 int rt_set_pixel_cost(void* buffer, uint64_t bytes) {

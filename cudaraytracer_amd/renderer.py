@@ -153,6 +153,45 @@ class DeviceScene:
             check(lib().rt_radiance_rays(self.handle, C.byref(a), C.c_void_p(stream)), "rt_radiance_rays")
         return out
 
+    def adaptive_samples(self, pixels, inputs: abi.InputStruct, width: int, height: int, depth: int = 8, samples=None,
+                         count=None, history=None, moments=None, accum=None, samples_per_pixel: int = 1,
+                         max_samples: int = 16, sample_base: int = 1, max_history: int = 32, seed: int = 1984,
+                         frame: int = 0, rays_per_lane: int = 0, left_to_right: bool = False, counters=None) -> None:
+        """The extra samples of a pixel list, traced and merged in place (rt_adaptive_samples), asynchronous on torch's
+        current stream.  pixels: a 32-bit integer (capacity,) device tensor of global pixel indices y * width + x, each
+        at most once; samples: the same shape, paths per entry (else samples_per_pixel each, at most max_samples);
+        count: a 32-bit integer device tensor whose first word is the number of entries (adaptive_select's; the host does
+        not read it), else every element of `pixels` is one.  Path j of an entry is sample sample_base + j of that
+        pixel's Philox stream (seed, pixel, frame).  Targets, float32 device tensors of the whole frame: history
+        (H, W, 4) with or without moments (H, W, 2), blended as further 1-spp frames of rt_temporal_moments would be;
+        accum (H, W, 4), added to as RT_FLAG_ACCUMULATE does."""
+        if pixels.dtype not in (torch.int32, torch.uint32) or pixels.dim() != 1 or not pixels.is_cuda or not pixels.is_contiguous():
+            raise ValueError("pixels must be a contiguous 32-bit integer (capacity,) tensor on the device")
+        if samples is not None and (samples.dtype not in (torch.int32, torch.uint32) or samples.shape != pixels.shape
+                                    or samples.device != pixels.device or not samples.is_contiguous()):
+            raise ValueError("samples must be a contiguous 32-bit integer tensor of pixels' shape on its device")
+        if count is not None and (count.dtype not in (torch.int32, torch.uint32) or count.numel() < 1
+                                  or count.device != pixels.device):
+            raise ValueError("count must be a 32-bit integer tensor on the pixels' device")
+        for name, plane, last in (("history", history, 4), ("moments", moments, 2), ("accum", accum, 4)):
+            if plane is not None and (plane.dtype != torch.float32 or plane.numel() != width * height * last
+                                      or plane.device != pixels.device or not plane.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of {height} x {width} x {last} on the pixels' device")
+        a = abi.AdaptiveSamplesArgs()
+        a.pixels = pixels.data_ptr()
+        for name, t in (("samples", samples), ("count", count), ("history", history), ("moments", moments),
+                        ("accum", accum), ("counters", counters)):
+            if t is not None:
+                setattr(a, name, t.data_ptr())
+        a.capacity, a.width, a.height = pixels.shape[0], width, height
+        a.samples_per_pixel, a.max_samples, a.sample_base = samples_per_pixel, max_samples, sample_base
+        a.max_depth, a.max_history, a.rays_per_lane = depth, max_history, rays_per_lane
+        a.flags = abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0
+        a.rng_seed, a.rng_frame = seed, frame
+        a.inputs = inputs
+        stream = torch.cuda.current_stream(pixels.device).cuda_stream
+        check(lib().rt_adaptive_samples(self.handle, C.byref(a), C.c_void_p(stream)), "rt_adaptive_samples")
+
     def close(self) -> None:
         if self.handle:
             lib().rt_scene_destroy(self.handle)
@@ -288,6 +327,9 @@ class Renderer:
         self.denoised_variance = None          # denoise_variance(): (local_rows × W × 4) float32, rgb + variance
         self._denoise_variance_scratch = None  # ... its planes, allocated once
         self._denoise_variance_pos = None
+        # adaptive_select(): the pixel list, its sample counts and (listed pixels, samples) on the device
+        self.adaptive_pixels = self.adaptive_samples = self.adaptive_count = None
+        self._adaptive_scratch = None
 
     def tiling(self) -> abi.Tiling:
         return abi.Tiling(self.band_rows, self.num_ranks, self.rank, self.local_rows)
@@ -494,6 +536,57 @@ class Renderer:
                 self._moments_spare, self.moments = self.moments, None
         self.history, self._history_spare = out, self.history
         return self._temporal_pos
+
+    def adaptive_select(self, tau: float = 0.1, min_history: int = 4, max_samples: int = 4, capacity: int | None = None,
+                        lum_floor: float = 0.01, pixels_per_lane: int = 0):
+        """Which pixels need how many more samples (rt_adaptive_select) by temporal(moments=True)'s `history` and
+        `moments` and the last gbuffer()'s prim_id (misses are never listed), asynchronous on torch's current stream;
+        whole frames only.  Returns the device tensors (pixels (capacity,) int32, samples (capacity,) int32, count (2,)
+        int32): the first min(count[0], capacity) entries are the pixels y * width + x with k > 0 in ascending order and
+        their k <= max_samples; count = (listed pixels in the frame, their k summed).  capacity defaults to the frame.
+        The tensors are the renderer's (`adaptive_pixels`, `adaptive_samples`, `adaptive_count`) and are reused by the
+        next call of the same capacity."""
+        if self.history is None or self.moments is None:
+            raise RTError("adaptive_select: no history and moments planes (call temporal(moments=True) first)")
+        n = self.width * self.local_rows
+        capacity = n if capacity is None else int(capacity)
+        if self.adaptive_pixels is None or self.adaptive_pixels.shape[0] != capacity:
+            self.adaptive_pixels = torch.zeros(capacity, dtype=torch.int32, device=self.device)
+            self.adaptive_samples = torch.zeros(capacity, dtype=torch.int32, device=self.device)
+        if self.adaptive_count is None:
+            self.adaptive_count = torch.zeros(2, dtype=torch.int32, device=self.device)
+            need = int(lib().rt_adaptive_select_scratch_bytes(self.width, self.height))
+            self._adaptive_scratch = torch.zeros(max(need, 4), dtype=torch.uint8, device=self.device)
+        a = abi.AdaptiveSelectArgs()
+        a.history, a.moments = self.history.data_ptr(), self.moments.data_ptr()
+        a.prim_id = self.prim_id.data_ptr() if self.prim_id is not None else None
+        if capacity:
+            a.pixels, a.samples = self.adaptive_pixels.data_ptr(), self.adaptive_samples.data_ptr()
+        a.count, a.scratch = self.adaptive_count.data_ptr(), self._adaptive_scratch.data_ptr()
+        a.width, a.height, a.capacity = self.width, self.height, capacity
+        a.max_samples, a.min_history, a.tau, a.lum_floor = max_samples, min_history, tau, lum_floor
+        a.pixels_per_lane = pixels_per_lane
+        a.tiling = self.tiling()
+        check(lib().rt_adaptive_select(C.byref(a), C.c_void_p(self.stream())), "rt_adaptive_select")
+        return self.adaptive_pixels, self.adaptive_samples, self.adaptive_count
+
+    def adaptive(self, scene: DeviceScene, inputs: abi.InputStruct, depth: int, tau: float = 0.1, min_history: int = 4,
+                 max_samples: int = 4, capacity: int | None = None, frame: int | None = None, seed: int | None = None,
+                 sample_base: int = 1, max_history: int = 32, lum_floor: float = 0.01) -> torch.Tensor:
+        """Adaptive sampling on the device: adaptive_select(), then DeviceScene.adaptive_samples() on the list, merged
+        into the current `history` and `moments` planes in place.  Call after temporal(moments=True) and before
+        denoise_variance(); whole frames only.  The extra samples of a pixel are samples sample_base .. of the Philox
+        stream (seed, pixel, frame): with the defaults — the renderer's seed, the frame render() drew last, sample 1 on
+        — they continue a 1-spp Philox frame.  max_history is temporal()'s.  Nothing is synchronised: returns the
+        device `count` tensor (listed pixels, extra samples)."""
+        pixels, samples, count = self.adaptive_select(tau, min_history, max_samples, capacity, lum_floor)
+        if pixels.shape[0]:
+            scene.adaptive_samples(pixels, inputs, self.width, self.height, depth, samples=samples, count=count,
+                                   history=self.history, moments=self.moments, max_samples=max_samples,
+                                   sample_base=sample_base, max_history=max_history,
+                                   seed=self.seed if seed is None else seed,
+                                   frame=max(self.frame - 1, 0) if frame is None else frame)
+        return count
 
     def denoise_variance(self, iterations: int = 3, sigma_l: float = 1.0, sigma_n: float = 0.1, sigma_z: float = 0.05,
                          min_history: int = 4) -> np.ndarray:

@@ -188,8 +188,8 @@ const char* rt_version(void);
  * rt_trace_rays take scenes with 32-bit BVH references; later additions that change no structure layout, counter
  * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells,
  * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays, rt_camera_rays, rt_radiance_rays,
- * rt_set_bounce_classes, rt_bounce_class_entries_host (a caller asks the
- * library for them by name). */
+ * rt_set_bounce_classes, rt_bounce_class_entries_host, rt_adaptive_select, rt_adaptive_select_scratch_bytes,
+ * rt_adaptive_samples (a caller asks the library for them by name). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
@@ -759,6 +759,109 @@ typedef struct rt_denoise_variance_args {
 uint64_t rt_denoise_variance_scratch_bytes(uint32_t width, uint32_t height, uint32_t iterations);
 /* The filter on `stream`, asynchronous; status codes and rt_last_error as rt_render. */
 int rt_denoise_variance(const rt_denoise_variance_args* args, rt_stream stream);
+
+/* ------------------------------------------------------------------------------------------------ */
+/* Adaptive sampling on the device: extra samples where rt_temporal_moments' planes say a pixel is     */
+/* noisy, merged into the history as further frames would have been. */
+/* A viewer calls both between rt_temporal_moments and rt_denoise_variance.                             */
+/* ------------------------------------------------------------------------------------------------ */
+
+/* Which pixels of a whole frame (height × width planes, row 0 at the bottom, as rt_temporal) need how many more
+ * samples.  Per pixel p, in binary32 with one rounding per operation and no contraction, max(a, b) = a > b ? a : b:
+ *   N = max(history(p).w, 1),  v = max(m2 − m1·m1, 0),  m = max(m1, lum_floor),  T = (tau·tau)·(m·m),
+ *   k(p) = #{ j in [0, max_samples) : N + (float)j < (float)min_history  or  v > (N + (float)j)·T },
+ *   k(p) = 0 where prim_id(p) < 0 (prim_id == NULL: every pixel is valid).
+ * Both predicates fall in j, so k(p) is the number of extra samples after which the pixel's history is min_history long
+ * and the variance of its mean is within (tau·m)²: tau is the relative standard error asked for.  Only multiplications,
+ * additions and comparisons: a float32 restatement gives the same k bit for bit.  A NaN compares false.
+ *   pixels[i], samples[i]: the global index y·width + x and k of the i-th pixel with k > 0 in ascending index order,
+ *   for i < min(count[0], capacity); elements beyond are not written.  The list does not depend on the launch shape.
+ *   count[0]: the number of pixels with k > 0 in the frame (it may exceed capacity: the list is then cut, in index
+ *   order); count[1]: the sum of k over all of them.
+ * Two asynchronous launches on `stream`, in neither of which a workgroup waits for another, no atomics: per-workgroup
+ * counts into `scratch`; then every workgroup sums the counts before its own (the scan) and writes its pixels in order.
+ * scratch: device memory of rt_adaptive_select_scratch_bytes(width, height) bytes, 4-byte aligned (NULL only when that
+ * is 0).  pixels_per_lane changes the launch shape only.
+ * RT_ERR_INVALID_ARGUMENT, before any device call: NULL args; tau or lum_floor not > 0; min_history above 4096;
+ * max_samples outside 1..16; pixels_per_lane above 16; non-zero flags or reserved words; tiling.num_ranks > 1 or
+ * local_rows neither 0 nor height; width·height·max_samples beyond 32 bits; with a non-empty frame: NULL count,
+ * history, moments or scratch, and NULL pixels with capacity > 0; an output (pixels, samples, count, scratch) that
+ * overlaps an input or another output.  width·height = 0 or capacity = 0: RT_OK, and count is still written: (0, 0) for
+ * an empty frame (one memset; count may be NULL there, and nothing is written), the frame's counts for an empty list
+ * (pixels may be NULL there). */
+typedef struct rt_adaptive_select_args {
+    const float*   history;    /* float4: rt_temporal's plane; only .w, the history length, is read */
+    const float*   moments;    /* float2: rt_temporal_moments' plane of the same frame */
+    const int32_t* prim_id;    /* optional: rt_gbuffer_args.prim_id */
+    uint32_t* pixels;          /* out, device uint32[capacity] */
+    uint32_t* samples;         /* optional out, device uint32[capacity] */
+    uint32_t* count;           /* out, device uint32[2] */
+    void*     scratch;         /* rt_adaptive_select_scratch_bytes */
+    uint32_t width, height;
+    uint32_t capacity;
+    uint32_t max_samples;      /* 1..16 */
+    uint32_t min_history;      /* 0..4096 */
+    float tau, lum_floor;      /* both > 0; start from 0.1 and 0.01 */
+    uint32_t pixels_per_lane;  /* 0 = automatic, 1..16 */
+    uint32_t flags;            /* must be 0 */
+    uint32_t reserved[3];      /* must be 0 */
+    rt_tiling tiling;          /* whole frame only, as rt_temporal */
+} rt_adaptive_select_args;     /* 120 B */
+/* Bytes of rt_adaptive_select_args.scratch for a frame (0 for an empty frame). */
+uint64_t rt_adaptive_select_scratch_bytes(uint32_t width, uint32_t height);
+int rt_adaptive_select(const rt_adaptive_select_args* args, rt_stream stream);
+
+/* The extra samples of a pixel list, traced and merged in one launch.  Entry i (i below the entry count: min(count[0],
+ * capacity) with count[0] read from the device by the kernel — the host launches for capacity and never synchronises —
+ * or capacity itself with count == NULL, for a list of the caller's) is pixel pixels[i] with
+ * k_i = min(samples ? samples[i] : samples_per_pixel, max_samples) paths.  An entry with pixels[i] >= width·height or
+ * k_i = 0 is skipped.  Each pixel may be listed at most once, as rt_adaptive_select guarantees; with duplicates those
+ * pixels' results are unspecified and nothing else is touched.
+ * Path j of entry i is sample s = sample_base + j of that pixel: the camera ray of Kernel.cu:139-146 from the jitter in
+ * block 0 of sample s's window of the Philox stream (rng_seed, pixel, rng_frame) — rt_camera_rays' ray, generated in
+ * registers — then color() from block 1, each closest hit with rt_trace_rays' semantics, rays starting at the BVH root
+ * (rt_radiance_rays' definition): exactly the path an RT_FLAG_RNG_PHILOX frame runs for that pixel's sample s, and
+ * c_s = quant(contribution) / 4096 per channel the radiance a 1-spp frame writes.  The sky is inputs.background_*.
+ * Merge, into the pixel's own elements, read and written by the lane that traced it; at least one target:
+ *   history (float4, in place), optionally with moments (float2, in place; requires history).  For j = 0 .. k_i−1 in
+ *   order: N = min(history.w + 1, max_history), alpha = 1 / N (IEEE), h = h + alpha·(c_s − h) per channel,
+ *   M = M + alpha·((l, l·l) − M) with l rt_temporal_moments' luminance of c_s, history.w = N: step 5 of rt_temporal /
+ *   rt_temporal_moments for a resting camera, so the pixel ends where k_i further 1-spp frames would have left it.  The
+ *   incoming history.w is used as it is, 0 included.
+ *   accum (float4, in place): rgb += (the saturating sum of the k_i samples' 2^-12 units) / 4096, one float add per
+ *   channel, w += k_i: what RT_FLAG_ACCUMULATE adds for k_i samples.
+ * counters[0]: color() iterations, counters[3]: paths; count_tests as rt_radiance_rays.  flags: 0 or
+ * RT_FLAG_RIUS_LEFT_TO_RIGHT.  The result does not depend on rays_per_lane, on rt_set_tuning or on the call.
+ * RT_ERR_INVALID_ARGUMENT, before any device call and before the scene is read: NULL scene, NULL args, no target,
+ * moments without history, samples_per_pixel = 0 without samples, max_samples outside 1..16, sample_base + max_samples
+ * above RT_PHILOX_MAX_SPP, max_history outside 1..4096, rays_per_lane above 16, count_tests other than 0 or 1 or 1
+ * without counters, other flag bits, non-zero reserved words, width·height beyond 31 bits; with capacity > 0: NULL
+ * pixels, a zero width or height, any two of pixels, samples, count, counters, history, moments and accum that overlap.
+ * capacity = 0: RT_OK.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED. */
+typedef struct rt_adaptive_samples_args {
+    const uint32_t* pixels;     /* device uint32[capacity]: global pixel indices y·width + x, each at most once */
+    const uint32_t* samples;    /* optional device uint32[capacity]: paths per entry */
+    const uint32_t* count;      /* optional device uint32: [0] = the entry count (rt_adaptive_select's) */
+    float* history;             /* optional in/out, float4 plane: rt_temporal's */
+    float* moments;             /* optional in/out, float2 plane: rt_temporal_moments' (with history) */
+    float* accum;               /* optional in/out, float4 plane: RT_FLAG_ACCUMULATE's */
+    uint64_t* counters;         /* optional device uint64[RT_COUNTERS_WORDS] (added to, not cleared) */
+    uint32_t capacity;
+    uint32_t width, height;
+    uint32_t samples_per_pixel; /* paths per entry without `samples` */
+    uint32_t max_samples;       /* 1..16: the cap on an entry's paths */
+    uint32_t sample_base;       /* path j is the pixel's sample sample_base + j */
+    uint32_t max_depth;
+    uint32_t max_history;       /* 1..4096, as rt_temporal_args */
+    uint32_t rays_per_lane;     /* entries per lane: 0 = automatic, 1..16 (changes the schedule only) */
+    uint32_t count_tests;       /* 0 or 1 */
+    uint32_t flags;             /* 0 or RT_FLAG_RIUS_LEFT_TO_RIGHT */
+    uint32_t rng_frame;
+    uint64_t rng_seed;
+    rt_input_struct inputs;     /* the frame's camera and sky */
+    uint32_t reserved[2];       /* must be 0 */
+} rt_adaptive_samples_args;     /* 192 B */
+int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* args, rt_stream stream);
 
 /* Tuning/benchmark knob (per thread): the kernel rt_render launches.  -1 = automatic: 3 from 64 spp; below,
  * the faster of 3 and 4 as timed on the first frames of each (device, stream, scene, frame shape, spp, depth,

@@ -83,6 +83,8 @@ EXPORTED = [
     "rt_adaptive_select",
     "rt_adaptive_select_scratch_bytes",
     "rt_adaptive_samples",
+    "rt_temporal_gradient",
+    "rt_history_adapt",
 ]
 
 _lib = None
@@ -181,6 +183,9 @@ def _declare(lib: C.CDLL) -> None:
         lib.rt_adaptive_select_scratch_bytes.argtypes = [C.c_uint32, C.c_uint32]
         lib.rt_adaptive_select_scratch_bytes.restype = C.c_uint64
         lib.rt_adaptive_samples.argtypes = [vp, P(abi.AdaptiveSamplesArgs), vp]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_temporal_gradient"):  # (an A/B build of an older revision lacks them)
+        lib.rt_temporal_gradient.argtypes = [vp, P(abi.TemporalGradientArgs), vp]
+        lib.rt_history_adapt.argtypes = [P(abi.HistoryAdaptArgs), vp]
     lib.LaunchKernel.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, abi.InputStruct]
     lib.LaunchKernel.restype = None
     lib.LaunchRandInit.argtypes = [vp]

@@ -32,7 +32,8 @@ RT_TEMPORAL_RESET = 1 << 1
 # rt_denoise_variance_scratch_bytes; 14: rt_query_rays, 32-bit references in rt_gbuffer and rt_trace_rays
 # (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells, rt_occluded_rays, rt_camera_rays,
 # rt_radiance_rays, rt_set_bounce_classes, rt_bounce_class_entries_host, rt_adaptive_select,
-# rt_adaptive_select_scratch_bytes and rt_adaptive_samples were added without a new number: no layout changed)
+# rt_adaptive_select_scratch_bytes, rt_adaptive_samples, rt_temporal_gradient and rt_history_adapt were added without a
+# new number: no layout changed)
 ABI_VERSION = 14
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)
@@ -321,6 +322,52 @@ class AdaptiveSamplesArgs(C.Structure):
         ("rng_frame", C.c_uint32),
         ("rng_seed", C.c_uint64),
         ("inputs", InputStruct),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class TemporalGradientArgs(C.Structure):
+    """rt_temporal_gradient_args, 192 bytes."""
+
+    _fields_ = [
+        ("prev_color", C.c_void_p),
+        ("gradient", C.c_void_p),
+        ("resample", C.c_void_p),
+        ("pixel", C.c_void_p),
+        ("counters", C.c_void_p),
+        ("rng_seed", C.c_uint64),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("offset_x", C.c_uint32),
+        ("offset_y", C.c_uint32),
+        ("samples_per_pixel", C.c_uint32),
+        ("max_depth", C.c_uint32),
+        ("rays_per_lane", C.c_uint32),
+        ("count_tests", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("rng_frame", C.c_uint32),
+        ("reserved", C.c_uint32 * 3),
+        ("tiling", Tiling),
+        ("inputs", InputStruct),
+    ]
+
+
+class HistoryAdaptArgs(C.Structure):
+    """rt_history_adapt_args, 72 bytes."""
+
+    _fields_ = [
+        ("gradient", C.c_void_p),
+        ("history", C.c_void_p),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("stride", C.c_uint32),
+        ("radius", C.c_uint32),
+        ("power", C.c_uint32),
+        ("gain", C.c_float),
+        ("lum_floor", C.c_float),
+        ("flags", C.c_uint32),
+        ("tiling", Tiling),
         ("reserved", C.c_uint32 * 2),
     ]
 

@@ -4415,6 +4415,131 @@ __global__ __launch_bounds__(64, 4) void adaptive_samples_kernel(const AdaptiveP
 }
 
 // ---------------------------------------------------------------------------------------------------
+// A past frame's samples traced again in the scene as it is now, and compared with what that frame stored
+// (rt_temporal_gradient): adaptive_samples_kernel's schedule with strata as work items.  Stratum i = sy·sw + sx owns one
+// pixel of its stride × stride block, (min(sx·stride + off_x, W − 1), min(sy·stride + off_y, H − 1)); a lane owns the
+// stratum from the first camera ray of sample 0 to its store.  Path j is the pixel's sample j of the Philox stream
+// (key, pixel, frame): camera_ray from block 0 of the sample's window, the bounce loop from block 1, rays from the root,
+// the geometric closest hit — the path that frame ran, so a path that meets nothing edited returns that frame's bits
+// and the difference is an exact zero.  No history, no moments: the lane carries the three sums alone.  Every element
+// is written by the lane that traced the stratum, so the result does not depend on the schedule.
+// ---------------------------------------------------------------------------------------------------
+struct GradientParams {
+    KParams K;
+    const float4* prev_color;
+    float2* gradient;
+    float4* resample;
+    uint32_t* pixel;
+    uint32_t n, per_wave;  // strata: sw · sh of them
+    uint32_t sw, stride, off_x, off_y;
+    uint32_t samples;
+};
+static_assert(offsetof(GradientParams, K) == 0, "philox_block and kparams_reload read the kernel arguments as a KParams");
+
+template <bool COUNT_TESTS, bool WIDE>
+__global__ __launch_bounds__(64, 4) void temporal_gradient_kernel(const GradientParams Q) {
+    using Entry = typename RefW<WIDE>::Entry;
+    const KParams* P = &Q.K;
+    extern __shared__ float4 lds[];
+    const uint32_t lane = threadIdx.x & 63u;
+    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
+    const __amdgpu_buffer_rsrc_t nrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+    stk[0] = (Entry)RefW<WIDE>::kSentinel;
+    stk[64] = (Entry)RefW<WIDE>::kSentinel;
+    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
+    const uint32_t count = min(Q.n - base, Q.per_wave);  // strata of this wave's range
+    Counts cnt{0, 0, 0, 0, 0, 0, 0};
+    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+    uint32_t nrays = 0u, npaths = 0u;
+    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
+    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the stratum's sample sums, 2^-12 units
+    uint32_t item = 0u, pixel = 0u, sample = 0u, depth = 0u;
+    RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
+    const bool rtl = P->rius_rtl != 0;
+    // the pixel's path of sample `sample` starts: its own camera ray, then block 1 of the sample's window
+    const auto begin_path = [&]() {
+        KParamsC* const q = kparams_reload();
+        const uint32_t g = pixel / q->width, x = pixel - g * q->width;
+        camera_ray(q, lane_camera(q, x, g), rng, ro, rd, sample);
+        att = mk(1.0f, 1.0f, 1.0f);
+        depth = 0u;
+        npaths++;
+        v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+    };
+    const auto store = [&]() {
+        const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
+        const float ns = (float)Q.samples;
+        const f3 cn = divs_rn(s, ns, recip_in_range(ns));  // rt_radiance_rays' mean
+        const float4 co = Q.prev_color[pixel];             // (pixel < W·H: both coordinates are clamped)
+        const float delta = (fabsf(cn.x - co.x) + fabsf(cn.y - co.y)) + fabsf(cn.z - co.z);
+        const float level = ((cn.x > co.x ? cn.x : co.x) + (cn.y > co.y ? cn.y : co.y)) + (cn.z > co.z ? cn.z : co.z);
+        Q.gradient[item] = make_float2(delta, level);  // (item < n: start() is called for indices below count alone)
+        if (Q.resample) Q.resample[item] = make_float4(cn.x, cn.y, cn.z, 1.0f);
+        if (Q.pixel) Q.pixel[item] = pixel;
+        c.mode = MODE_NEED;
+    };
+    const auto start = [&](uint32_t i) {
+        item = i;
+        const uint32_t sy = i / Q.sw, sx = i - sy * Q.sw;
+        pixel = min(sy * Q.stride + Q.off_y, P->height - 1u) * P->width + min(sx * Q.stride + Q.off_x, P->width - 1u);
+        rng.pix = pixel;
+        q0 = q1 = q2 = 0u;
+        sample = 0u;
+        if (P->max_depth != 0u) {
+            begin_path();
+        } else {  // exceeded recursion at once (Kernel.cu:79): every sample is 0, nothing is traced
+            npaths += Q.samples;
+            c.mode = MODE_ENDED;
+        }
+    };
+    if (lane < count) start(base + lane);
+    uint32_t taken = 64u;  // wave-uniform: strata of the wave's range handed out so far
+    while (__ballot(c.mode != MODE_DONE) != 0) {
+        if (c.mode == MODE_TRAV) {
+            uint32_t thr = P->regen_threshold;
+            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c, cnt, 64u,
+                                                                P->leaf_break);
+        }
+        if (c.mode == MODE_SHADE) {
+            if (COUNT_TESTS) cnt.wshade += wave_leader();
+            KParamsC* const q = kparams_reload();
+            f3 contrib;
+            const int res = shade<true, false, false>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att, rng, rtl,
+                                                      contrib);
+            bool ended = res == SHADE_ENDED;
+            if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
+                ended = true;
+                contrib = mk(0.0f, 0.0f, 0.0f);
+            }
+            if (!ended) {
+                v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+            } else {
+                q0 = sat_add(q0, quant12(contrib.x));
+                q1 = sat_add(q1, quant12(contrib.y));
+                q2 = sat_add(q2, quant12(contrib.z));
+                if (++sample < Q.samples) begin_path();
+                else c.mode = MODE_ENDED;
+            }
+        }
+        if (c.mode == MODE_ENDED) store();
+        const uint64_t needm = __ballot(c.mode == MODE_NEED);
+        if (needm != 0) {
+            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
+            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
+            if (c.mode == MODE_NEED) {
+                if (k < count) start(base + k);
+                else c.mode = MODE_DONE;
+            }
+        }
+    }
+    cnt.rays = nrays;
+    cnt.primary = npaths;
+    flush_counts<COUNT_TESTS>(*P, cnt);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The camera rays of the render kernels as a ray batch (rt_camera_rays): one lane per ray, camera_ray / camera_ray_at
 // and lane_camera themselves.  rays[2i] = (origin, kTmin), rays[2i + 1] = (direction, FLT_MAX): color()'s range.  The
 // params begin with a KParams (camera_ray's Philox draw reads key and frame through the kernel-argument pointer).
@@ -5621,6 +5746,79 @@ int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a
                                     : (a->count_tests ? dev::adaptive_samples_kernel<true, false> : dev::adaptive_samples_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
     return hip_check(hipGetLastError(), "rt_adaptive_samples: kernel launch", RT_ERR_LAUNCH);
+}
+
+int rt_temporal_gradient(const rt_scene* scene, const rt_temporal_gradient_args* a, rt_stream stream) {
+    // (every argument check runs before the first device call and before the scene is read)
+    const auto bad = [](const std::string& what) {
+        set_error("rt_temporal_gradient: " + what);
+        return (int)RT_ERR_INVALID_ARGUMENT;
+    };
+    if (!a) return bad("NULL args");
+    if ((a->flags & ~(uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT) != 0) return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT");
+    if (a->reserved[0] != 0 || a->reserved[1] != 0 || a->reserved[2] != 0) return bad("reserved must be 0");
+    if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
+    if (a->count_tests > 1u) return bad("count_tests must be 0 or 1");
+    if (a->count_tests && !a->counters) return bad("count_tests without counters");
+    if (a->stride < 1u || a->stride > 8u) return bad("stride must be 1..8");
+    if (a->offset_x >= a->stride) return bad("offset_x must be below stride");
+    if (a->offset_y >= a->stride) return bad("offset_y must be below stride");
+    if (a->samples_per_pixel < 1u || a->samples_per_pixel > 16u) return bad("samples_per_pixel must be 1..16");
+    if (a->tiling.num_ranks > 1) return bad("the pass works on a whole frame (tiling.num_ranks > 1)");
+    if (a->tiling.local_rows != 0 && a->tiling.local_rows != a->height) return bad("tiling.local_rows is not the frame's height");
+    const uint64_t n = (uint64_t)a->width * a->height;
+    if (n > 0x7fffffffull) return bad("frame too large (width * height)");
+    if (n == 0) return RT_OK;  // no stratum
+    const uint32_t sw = (a->width + a->stride - 1u) / a->stride, sh = (a->height + a->stride - 1u) / a->stride;
+    const uint64_t strata = (uint64_t)sw * sh;
+    if (!a->prev_color) return bad("NULL prev_color");
+    if (!a->gradient) return bad("NULL gradient");
+    const char* const names[5] = {"prev_color", "gradient", "resample", "pixel", "counters"};
+    const void* const bufs[5] = {a->prev_color, a->gradient, a->resample, a->pixel, a->counters};
+    const uint64_t bytes[5] = {n * 16u, strata * 8u, strata * 16u, strata * 4u, (uint64_t)RT_COUNTERS_WORDS * 8u};
+    for (int i = 0; i < 5; i++)
+        for (int j = 0; j < i; j++)
+            if (overlaps(bufs[i], bytes[i], bufs[j], bytes[j])) return bad(std::string(names[i]) + " overlaps " + names[j]);
+    if (!scene) return bad("NULL scene");
+    const DeviceScene& S = scene->dev;
+    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
+    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_temporal_gradient: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    dev::GradientParams Q;
+    std::memset(&Q, 0, sizeof(Q));
+    dev::KParams& P = Q.K;
+    fill_scene_tables(P, S);
+    P.width = a->width;  // (global indices: one band of the whole frame, as rt_adaptive_samples)
+    P.height = a->height;
+    P.band_rows = 1u;
+    P.num_ranks = 1u;
+    fill_camera(P, a->inputs, a->width, a->height);  // (the sky too)
+    P.counters = (unsigned long long*)a->counters;
+    P.regen_threshold = (uint32_t)g_regen_threshold;
+    P.regen_live_frac = (uint32_t)g_regen_live_frac;
+    P.leaf_break = (uint32_t)g_leaf_break;
+    P.max_depth = a->max_depth;
+    P.rius_rtl = (a->flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
+    P.rng_key_lo = (uint32_t)a->rng_seed;
+    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
+    P.rng_frame = a->rng_frame;
+    Q.prev_color = (const float4*)a->prev_color;
+    Q.gradient = (float2*)a->gradient;
+    Q.resample = (float4*)a->resample;
+    Q.pixel = a->pixel;
+    Q.n = (uint32_t)strata;
+    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(Q.n));
+    Q.sw = sw;
+    Q.stride = a->stride;
+    Q.off_x = a->offset_x;
+    Q.off_y = a->offset_y;
+    Q.samples = a->samples_per_pixel;
+    const uint32_t grid = (uint32_t)((strata + Q.per_wave - 1) / Q.per_wave);
+    hipStream_t s = (hipStream_t)stream;
+    (void)hipGetLastError();
+    const auto kernel = S.wide_refs ? (a->count_tests ? dev::temporal_gradient_kernel<true, true> : dev::temporal_gradient_kernel<false, true>)
+                                    : (a->count_tests ? dev::temporal_gradient_kernel<true, false> : dev::temporal_gradient_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
+    return hip_check(hipGetLastError(), "rt_temporal_gradient: kernel launch", RT_ERR_LAUNCH);
 }
 
 int rt_set_pixel_cost(void* buffer, uint64_t bytes) {

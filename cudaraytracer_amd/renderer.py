@@ -192,6 +192,44 @@ class DeviceScene:
         stream = torch.cuda.current_stream(pixels.device).cuda_stream
         check(lib().rt_adaptive_samples(self.handle, C.byref(a), C.c_void_p(stream)), "rt_adaptive_samples")
 
+    def temporal_gradient(self, prev_color, inputs: abi.InputStruct, width: int, height: int, depth: int = 8,
+                          stride: int = 3, offset=(0, 0), samples_per_pixel: int = 1, seed: int = 1984, frame: int = 0,
+                          gradient=None, resample=None, pixel=None, rays_per_lane: int = 0,
+                          left_to_right: bool = False, counters=None):
+        """A past Philox frame's samples traced again in this scene and compared with what that frame stored
+        (rt_temporal_gradient), asynchronous on torch's current stream.  prev_color: that frame's radiance plane, a
+        float32 device tensor of H x W x 4; inputs, seed, frame, samples_per_pixel, depth and left_to_right are that
+        frame's.  One pixel per stride x stride stratum, at `offset` = (offset_x, offset_y) inside it.  Outputs, device
+        tensors over the ceil(H / stride) x ceil(W / stride) strata: gradient (.., 2) float32 (allocated when None),
+        resample (.., 4) float32 and pixel (..) 32-bit integers, both optional.  Returns gradient."""
+        if (prev_color.dtype != torch.float32 or prev_color.numel() != width * height * 4 or not prev_color.is_cuda
+                or not prev_color.is_contiguous()):
+            raise ValueError(f"prev_color must be a contiguous float32 tensor of {height} x {width} x 4 on the device")
+        if not 1 <= stride <= 8:
+            raise ValueError("stride must be 1..8")
+        sw, sh = -(-width // stride), -(-height // stride)
+        if gradient is None:
+            gradient = torch.empty((sh, sw, 2), dtype=torch.float32, device=prev_color.device)
+        for name, t, dtypes, last in (("gradient", gradient, (torch.float32,), 2), ("resample", resample, (torch.float32,), 4),
+                                      ("pixel", pixel, (torch.int32, torch.uint32), 1)):
+            if t is not None and (t.dtype not in dtypes or t.numel() != sw * sh * last or t.device != prev_color.device
+                                  or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous tensor of {sh} x {sw} x {last} on prev_color's device")
+        a = abi.TemporalGradientArgs()
+        a.prev_color, a.gradient = prev_color.data_ptr(), gradient.data_ptr()
+        for name, t in (("resample", resample), ("pixel", pixel), ("counters", counters)):
+            if t is not None:
+                setattr(a, name, t.data_ptr())
+        a.width, a.height, a.stride, a.offset_x, a.offset_y = width, height, stride, int(offset[0]), int(offset[1])
+        a.samples_per_pixel, a.max_depth, a.rays_per_lane = samples_per_pixel, depth, rays_per_lane
+        a.flags = abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0
+        a.rng_seed, a.rng_frame = seed, frame
+        a.tiling = abi.Tiling(max(height, 1), 1, 0, height)
+        a.inputs = inputs
+        stream = torch.cuda.current_stream(prev_color.device).cuda_stream
+        check(lib().rt_temporal_gradient(self.handle, C.byref(a), C.c_void_p(stream)), "rt_temporal_gradient")
+        return gradient
+
     def close(self) -> None:
         if self.handle:
             lib().rt_scene_destroy(self.handle)
@@ -330,6 +368,11 @@ class Renderer:
         # adaptive_select(): the pixel list, its sample counts and (listed pixels, samples) on the device
         self.adaptive_pixels = self.adaptive_samples = self.adaptive_count = None
         self._adaptive_scratch = None
+        # temporal_gradient(): the (strata rows × strata columns × 2) plane of the last call, the frame that wrote the
+        # `radiance` plane (inputs, seed, frame, spp, flags; None after an XORWOW frame) and the calls so far
+        self.gradient = None
+        self._radiance_frame = None
+        self._gradient_calls = 0
 
     def tiling(self) -> abi.Tiling:
         return abi.Tiling(self.band_rows, self.num_ranks, self.rank, self.local_rows)
@@ -384,6 +427,9 @@ class Renderer:
         a.tiling = self.tiling()
         a.inputs = inputs
         check(lib().rt_render(scene.handle, C.byref(a), C.c_void_p(self.stream())), "rt_render")
+        if radiance:  # what temporal_gradient() needs to trace this frame's paths again
+            self._radiance_frame = ((abi.InputStruct.from_buffer_copy(inputs), self.seed, frame, spp, flags)
+                                    if self.rng == "philox" else None)
         return self.pos
 
     def reset_accumulation(self) -> None:
@@ -587,6 +633,47 @@ class Renderer:
                                    seed=self.seed if seed is None else seed,
                                    frame=max(self.frame - 1, 0) if frame is None else frame)
         return count
+
+    def temporal_gradient(self, scene: DeviceScene, depth: int, stride: int = 3, radius: int = 1, power: int = 4,
+                          gain: float = 1.0, lum_floor: float = 0.01) -> torch.Tensor:
+        """Cut stale history after a scene edit (rt_temporal_gradient, then rt_history_adapt): call after the edit and
+        before the next render(), on frames with an edit only; whole frames only.  `scene` is the edited scene.  The
+        last render(..., radiance=True) — its `radiance` plane, inputs, seed, frame number, spp and fill order; it must
+        have been a Philox frame, and `depth` must be the depth it was drawn with — is traced again in `scene` at one
+        pixel per stride x stride stratum, and the current `history` plane's lengths are scaled in place by
+        (1 - lambda)^power, lambda from the strata within `radius` of the pixel's.  The pixel's place in its stratum
+        rotates through the stride^2 positions from call to call.  Nothing is synchronised: returns the device gradient
+        plane (strata rows, strata columns, 2), also kept as `self.gradient`."""
+        if self.radiance is None:
+            raise RTError("temporal_gradient: no radiance plane (render with radiance=True first)")
+        if self.history is None:
+            raise RTError("temporal_gradient: no history plane (call temporal() first)")
+        if self._radiance_frame is None:
+            raise RTError("temporal_gradient: the last render was not a Philox frame (an XORWOW frame cannot be traced again)")
+        if not 1 <= stride <= 8:
+            raise ValueError("stride must be 1..8")
+        inputs, seed, frame, spp, flags = self._radiance_frame
+        sw, sh = -(-self.width // stride), -(-self.local_rows // stride)
+        if self.gradient is None or tuple(self.gradient.shape) != (sh, sw, 2):
+            self.gradient = torch.zeros((sh, sw, 2), dtype=torch.float32, device=self.device)
+        turn = self._gradient_calls % (stride * stride)
+        self._gradient_calls += 1
+        a = abi.TemporalGradientArgs()
+        a.prev_color, a.gradient = self.radiance.data_ptr(), self.gradient.data_ptr()
+        a.width, a.height, a.stride, a.offset_x, a.offset_y = self.width, self.height, stride, turn % stride, turn // stride
+        a.samples_per_pixel, a.max_depth = spp, depth
+        a.flags = flags & abi.RT_FLAG_RIUS_LEFT_TO_RIGHT
+        a.rng_seed, a.rng_frame = seed, frame
+        a.tiling = self.tiling()
+        a.inputs = inputs
+        check(lib().rt_temporal_gradient(scene.handle, C.byref(a), C.c_void_p(self.stream())), "rt_temporal_gradient")
+        b = abi.HistoryAdaptArgs()
+        b.gradient, b.history = self.gradient.data_ptr(), self.history.data_ptr()
+        b.width, b.height, b.stride, b.radius, b.power = self.width, self.height, stride, radius, power
+        b.gain, b.lum_floor = gain, lum_floor
+        b.tiling = self.tiling()
+        check(lib().rt_history_adapt(C.byref(b), C.c_void_p(self.stream())), "rt_history_adapt")
+        return self.gradient
 
     def denoise_variance(self, iterations: int = 3, sigma_l: float = 1.0, sigma_n: float = 0.1, sigma_z: float = 0.05,
                          min_history: int = 4) -> np.ndarray:

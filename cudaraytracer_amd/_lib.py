@@ -85,6 +85,7 @@ EXPORTED = [
     "rt_adaptive_samples",
     "rt_temporal_gradient",
     "rt_history_adapt",
+    "rt_scene_lights_host",
 ]
 
 _lib = None
@@ -186,6 +187,8 @@ def _declare(lib: C.CDLL) -> None:
     if LIB_PATH == _IN_TREE or hasattr(lib, "rt_temporal_gradient"):  # (an A/B build of an older revision lacks them)
         lib.rt_temporal_gradient.argtypes = [vp, P(abi.TemporalGradientArgs), vp]
         lib.rt_history_adapt.argtypes = [P(abi.HistoryAdaptArgs), vp]
+    if LIB_PATH == _IN_TREE or hasattr(lib, "rt_scene_lights_host"):  # (an A/B build of an older revision lacks it)
+        lib.rt_scene_lights_host.argtypes = [P(abi.SceneDesc), P(C.c_uint32), C.c_uint32, P(C.c_uint32)]
     lib.LaunchKernel.argtypes = [vp, C.c_uint, C.c_uint, C.c_uint, C.c_uint, vp, vp, abi.InputStruct]
     lib.LaunchKernel.restype = None
     lib.LaunchRandInit.argtypes = [vp]

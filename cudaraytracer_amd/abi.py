@@ -23,6 +23,7 @@ RT_FLAG_RNG_PHILOX = 1 << 5
 RT_FLAG_STATE_SOA = 1 << 6
 RT_FLAG_ACCUMULATE_RESET = 1 << 7
 RT_CAMERA_JITTER_PHILOX = 1 << 0
+RT_RADIANCE_DIRECT_LIGHT = 1 << 8  # rt_radiance_args.flags: next-event estimation on the scene's light rectangles
 RT_DENOISE_DEMODULATE = 1 << 0
 RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0
@@ -32,8 +33,8 @@ RT_TEMPORAL_RESET = 1 << 1
 # rt_denoise_variance_scratch_bytes; 14: rt_query_rays, 32-bit references in rt_gbuffer and rt_trace_rays
 # (rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells, rt_occluded_rays, rt_camera_rays,
 # rt_radiance_rays, rt_set_bounce_classes, rt_bounce_class_entries_host, rt_adaptive_select,
-# rt_adaptive_select_scratch_bytes, rt_adaptive_samples, rt_temporal_gradient and rt_history_adapt were added without a
-# new number: no layout changed)
+# rt_adaptive_select_scratch_bytes, rt_adaptive_samples, rt_temporal_gradient, rt_history_adapt,
+# RT_RADIANCE_DIRECT_LIGHT and rt_scene_lights_host were added without a new number: no layout changed)
 ABI_VERSION = 14
 # entries (o.x, o.y, o.z, s) of the per-hittable motion table rt_scene_motion writes and rt_temporal_dynamic reads
 MOTION_NO_HISTORY = (0.0, 0.0, 0.0, 0.0)

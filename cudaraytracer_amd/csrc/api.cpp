@@ -80,6 +80,8 @@ static void free_device(DeviceScene* s) {
     if (s->prim_source) (void)hipFree((void*)s->prim_source);
     if (s->flat_source) (void)hipFree((void*)s->flat_source);
     s->prim_source = s->flat_source = nullptr;
+    if (s->light_table) (void)hipFree((void*)s->light_table);
+    s->light_table = nullptr;
     if (s->mats) (void)hipFree((void*)s->mats);
     if (s->imgs) (void)hipFree((void*)s->imgs);  // texels: owned by rt_scene::texel_block
     s->nodes = s->prims = s->mats = nullptr;
@@ -138,6 +140,10 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     d.prim_source = p;
     if ((rc = upload(h.flat_source, &p, "hipMalloc/hipMemcpy(flat_source)"))) goto fail;
     d.flat_source = p;
+    if ((rc = upload(h.light_table, &p, "hipMalloc/hipMemcpy(light_table)"))) goto fail;
+    d.light_table = p;
+    d.num_rects = (uint32_t)(h.rects.size() / 8);
+    d.num_lights = (uint32_t)h.lights.size();
     if ((rc = upload(h.mats, &p, "hipMalloc/hipMemcpy(materials)"))) goto fail;
     d.mats = p;
     if ((rc = upload(h.imgs, &p, "hipMalloc/hipMemcpy(images)"))) goto fail;
@@ -159,7 +165,7 @@ int create_device_scene(const HostScene& h, rt_scene** out, std::shared_ptr<void
     d.has_rects = h.has_rects;
     d.device_bytes = (h.nodes.size() + h.nodes48.size() + h.refs.size() + h.prims.size() + h.prims_flat.size() + h.ref_nodes.size() +
                       h.flat_boxes.size() + h.flat_ref_pairs.size() + h.bvh_ref_nodes.size() + h.bvh_boxes.size() + h.bvh_ref_pairs.size() + h.mats.size() +
-                      h.prim_source.size() + h.flat_source.size() + h.leaf_records.size() + h.class_records.size()) * 4 + h.bounce_grid.size() * 2 +
+                      h.prim_source.size() + h.flat_source.size() + h.leaf_records.size() + h.class_records.size() + h.light_table.size()) * 4 + h.bounce_grid.size() * 2 +
                      h.imgs.size() * 4 + h.texels.size();
     *out = s;
     return RT_OK;
@@ -498,6 +504,15 @@ int rt_scene_update_materials(rt_scene* scene, const rt_material_desc* materials
         scene->dev.has_image_textures = img;
         scene->dev.has_textures = tex;
         scene->host.mats = packed;
+        // a material edit can turn a rectangle into a sampled light or back: the list again, uploaded in place (the
+        // table holds an entry for every rectangle whatever the materials are)
+        build_light_table(&scene->host);
+        if (!scene->host.light_table.empty()) {
+            hipError_t e = hipMemcpy((void*)scene->dev.light_table, scene->host.light_table.data(),
+                                     scene->host.light_table.size() * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) return hip_fail(e, "rt_scene_update_materials: hipMemcpy(light_table)");
+        }
+        scene->dev.num_lights = (uint32_t)scene->host.lights.size();
         if (scene->described) scene->materials.assign(materials, materials + num_materials);  // what rt_scene_edit rebuilds from
         return RT_OK;
     });
@@ -552,6 +567,24 @@ int rt_build_host_tables(const rt_scene_desc* desc, float* nodes, float* prims, 
     if (prims) std::copy(h.prims.begin(), h.prims.begin() + (size_t)h.num_prims * 8, prims);
     if (materials) std::copy(h.mats.begin(), h.mats.end(), materials);
     if (prim_source) std::copy(h.prim_source.begin(), h.prim_source.end(), prim_source);
+    return RT_OK;
+}
+
+int rt_scene_lights_host(const rt_scene_desc* desc, uint32_t* hittables, uint32_t capacity, uint32_t* count) {
+    if (!count || (!hittables && capacity)) {
+        set_error("rt_scene_lights_host: NULL count, or NULL hittables with a capacity");
+        return RT_ERR_INVALID_ARGUMENT;
+    }
+    HostScene h;
+    int rc = guarded("rt_scene_lights_host", [&]() -> int {
+        std::string err;
+        int r = build_host_scene(desc, &h, &err, false);
+        if (r) set_error("rt_scene_lights_host: " + err);
+        return r;
+    });
+    if (rc) return rc;
+    *count = (uint32_t)h.lights.size();
+    std::copy(h.lights.begin(), h.lights.begin() + std::min<size_t>(h.lights.size(), capacity), hittables);
     return RT_OK;
 }
 

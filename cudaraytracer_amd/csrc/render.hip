@@ -914,10 +914,17 @@ enum ShadeResult { SHADE_CONTINUE = 0, SHADE_ENDED = 1, SHADE_DEFERRED = 2 };
 // EXACT (the BVH kernels): `hit` may carry kTieBit / kVerifiedBit; SHADE_REPLAY when the closest hit may not be the
 // reference's (bvh_clear) — nothing is changed, and the kernel replays the reference traversal (bvh_replay).
 enum { SHADE_REPLAY = 3 };
-template <bool TEX = true, bool DEFER = false, bool EXACT = false, class PP, class R>
+// VERTEX (radiance_direct_kernel): `vx` receives the vertex as Scatter sees it — the material class (0xff: a miss), for
+// a hit the HitRecord normal, and for a Lambertian or Metal hit that scatters the albedo texture value.
+struct ShadeVertex {
+    f3 normal, albedo;
+    uint32_t mtype;
+};
+template <bool TEX = true, bool DEFER = false, bool EXACT = false, bool VERTEX = false, class PP, class R>
 __device__ __forceinline__ int shade(PP P, const float4* __restrict__ prims, const float4* __restrict__ mats,
                                      const int4* __restrict__ imgs, int hit, uint32_t hit_tag, float t,
-                                     f3& ro, f3& rd, f3& att, R& rng, bool rtl, f3& contrib, uint32_t* const s2 = nullptr) {
+                                     f3& ro, f3& rd, f3& att, R& rng, bool rtl, f3& contrib, uint32_t* const s2 = nullptr,
+                                     ShadeVertex* const vx = nullptr) {
     float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = p0;
     // unit_vector(rd) is needed by the sky (y only), Metal and Dielectric: computed once for all lanes of
     // the wave that need it instead of once per material branch (same binary32 operations, Math.cuh:210-213)
@@ -940,6 +947,7 @@ __device__ __forceinline__ int shade(PP P, const float4* __restrict__ prims, con
         if (hit >= 0) mtype = __float_as_uint(mats[3 * (hit_tag >> 4)].x) & 15u;
     }
     const bool specular = mtype == RT_METAL || mtype == RT_DIELECTRIC;
+    if constexpr (VERTEX) vx->mtype = mtype;
     if (hit < 0) {  // sky (Kernel.cu:41-44)
         contrib = sky_contrib(P, rd, att);
         return SHADE_ENDED;
@@ -976,6 +984,7 @@ __device__ __forceinline__ int shade(PP P, const float4* __restrict__ prims, con
         normal = front ? outward : neg(outward);
         p = add(ro, scale(t, rd));
     }
+    if constexpr (VERTEX) vx->normal = normal;
     if (mtype == RT_DIFFUSELIGHT) {  // DiffuseLight::Emitted (Material.cuh:164-176)
         const float4 m1 = mats[3 * mat + 1];
         f3 tex = xyz(m1);
@@ -1046,6 +1055,7 @@ __device__ __forceinline__ int shade(PP P, const float4* __restrict__ prims, con
         q = random_in_unit_sphere(rng, rtl);
     }
     const f3 attenuation = texture_resolve(tex, texel_word);
+    if constexpr (VERTEX) vx->albedo = attenuation;
     bool ok = true;
     if (mtype == RT_LAMBERTIAN) {  // Lambertian::Scatter (Material.cuh:43-62)
         const f3 target = add(add(p, normal), q);
@@ -4265,6 +4275,224 @@ __global__ __launch_bounds__(64, 4) void radiance_rays_kernel(const RadiancePara
 }
 
 // ---------------------------------------------------------------------------------------------------
+// rt_radiance_rays with RT_RADIANCE_DIRECT_LIGHT (next-event estimation; rt_hip.h has the definition, DESIGN.md §20 the
+// density argument): radiance_rays_kernel's schedule and path, where a lane whose path continues from a Lambertian
+// vertex first traces a shadow ray to a point sampled on one of the scene's light rectangles — v3_traverse's ANYHIT
+// build over (1e-4, 0.9999) of the segment, as occlusion_rays_kernel runs it — and then its bounce ray, whose direction
+// waits in `bd`.  A wave's lanes are in either state at once: each traversal step runs the closest-hit lanes, then the
+// shadow lanes.  The weighted term waits in `pend` until the shadow ray has missed, the terms of a path are summed in
+// float in vertex order (`acc`), and the path's end adds its terminal term and quantises once.  A sampled light met
+// after a Lambertian scatter emits nothing (its light was counted at that vertex); every other emitter hit keeps its
+// emission.  The draws of vertex j are words 0..2 of block W + 65535 - j of the sample's window (max_depth <= 4096
+// keeps them apart from the path's, which grow from W + 1), so the path's own draws — and its vertices — are the
+// flagless call's.  The params begin with a RadianceParams, whose layout stays as it is.
+// ---------------------------------------------------------------------------------------------------
+struct RadianceDirectParams {
+    RadianceParams R;
+    const float4* lights;         // HostScene::light_table: two float4 per sampled light, in list order
+    const uint32_t* light_flags;  // ... and its word per primitive: 1 = a sampled light
+    uint32_t num_lights;          // N_L >= 1
+};
+static_assert(offsetof(RadianceDirectParams, R) == 0, "philox_block and kparams_reload read the kernel arguments as a KParams");
+
+// The connection from the Lambertian vertex (p, normal n) to a point of a sampled light, from the draws (xi0, xi1, xi2):
+// the segment v = y - p and the term's weight D per channel (rt_hip.h).  False where the connection cannot count
+// (c <= 0, c' <= 0 or a NaN).  y and v: one rounding per operation, in the header's order (no contraction).
+template <class PP>
+__device__ __forceinline__ bool light_connection(PP q, const float4* __restrict__ lights, const uint32_t nl, const float xi0,
+                                                 const float xi1, const float xi2, const f3 p, const f3 n, f3& v, f3& D) {
+    const uint32_t l = min((uint32_t)(xi0 * (float)nl), nl - 1u);
+    const float4 l0 = lights[2 * (size_t)l], l1 = lights[2 * (size_t)l + 1];  // (centre, width), (height, primitive, -, -)
+    const uint32_t lp = __float_as_uint(l1.y);
+    const float4 p0 = q->prims[2 * (size_t)lp], p1 = q->prims[2 * (size_t)lp + 1];
+    const uint32_t type = __float_as_uint(p1.w) & 15u, mat = __float_as_uint(p1.w) >> 4;
+    const float dw = (xi1 - 0.5f) * l0.w, dh = (xi2 - 0.5f) * l1.x;
+    f3 y = xyz(l0);
+    if (type == RT_XYRECT) {  // width along x, height along y
+        y.x = y.x + dw;
+        y.y = y.y + dh;
+    } else if (type == RT_XZRECT) {  // width along x, height along z
+        y.x = y.x + dw;
+        y.z = y.z + dh;
+    } else {  // RT_YZRECT: width along z, height along y
+        y.z = y.z + dw;
+        y.y = y.y + dh;
+    }
+    v = sub(y, p);
+    const float d2 = dot(v, v);
+    const float d = sqrt_fast(d2);
+    const float c = fdiv(dot(n, v), d);
+    const float va = type == RT_XYRECT ? v.z : (type == RT_XZRECT ? v.y : v.x);
+    const float cp = fdiv(fabsf(va), d);
+    if (!(c > 0.0f && cp > 0.0f)) return false;
+    // Le(y): DiffuseLight::Emitted at the (u, v) a hit at y would record (shade()'s rectangle record)
+    const float4 m0 = q->mats[3 * mat + 0], m1 = q->mats[3 * mat + 1];
+    const uint32_t ttype = (__float_as_uint(m0.x) >> 4) & 15u;
+    f3 tex = xyz(m1);
+    if (ttype != RT_CONSTANT) {
+        const float ya = type == RT_YZRECT ? y.y : y.x, yb = type == RT_XYRECT ? y.y : y.z;
+        const float hu = fdiv(ya - p0.y, p0.z - p0.y);
+        const float hv = fdiv(yb - p0.w, p1.x - p0.w);
+        const float4 m2 = q->mats[3 * mat + 2];
+        tex = texture_value(m0, m1, m2, ttype, hu, hv, y, q->imgs, q->texels);
+    }
+    const float g = fdiv(2.0f * (c * c * c) * cp * (l0.w * l1.x) * (float)nl, 3.141592654f * d2);
+    D = scale(g, scale(m0.z, tex));
+    return true;
+}
+
+typedef __attribute__((address_space(4))) const RadianceDirectParams RadianceDirectParamsC;  // (as KParamsC)
+
+// (The counting builds carry both traversals' diagnostic counts: they ask for two waves per SIMD, not four.)
+template <bool COUNT_TESTS, bool WIDE>
+__global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kernel(const RadianceDirectParams DQ) {
+    using Entry = typename RefW<WIDE>::Entry;
+    const RadianceParams& Q = DQ.R;
+    const KParams* P = &Q.K;
+    extern __shared__ float4 lds[];
+    const uint32_t lane = threadIdx.x & 63u;
+    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
+    const __amdgpu_buffer_rsrc_t nrsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+    stk[0] = (Entry)RefW<WIDE>::kSentinel;
+    stk[64] = (Entry)RefW<WIDE>::kSentinel;
+    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
+    const uint32_t count = min(Q.n - base, Q.per_wave);  // rays of this wave's range (base + per_wave may wrap)
+    Counts cnt{0, 0, 0, 0, 0, 0, 0};
+    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+    uint32_t ray = base + lane, nrays = 0u, npaths = 0u;
+    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
+    f3 acc = ro;   // the path's direct terms so far
+    f3 pend = ro;  // shadow state: the term the shadow ray decides
+    f3 bd = ro;    // shadow state: the bounce ray's direction
+    bool shadow = false;     // the lane traces (or has traced) a shadow ray
+    bool prev_lamb = false;  // the path's previous vertex was a Lambertian scatter
+    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the ray's sample sums, 2^-12 units
+    uint32_t sample = 0u, depth = 0u;
+    RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
+    const bool rtl = P->rius_rtl != 0;
+    // the lane's ray starts its path of sample `sample`
+    // (the call's own arguments are loaded where they are used, as shade() loads the scene's: held across the two
+    // traversals they would not fit the scalar registers)
+    const auto args = []() { return (RadianceDirectParamsC*)kparams_reload(); };
+    const auto begin_path = [&]() {
+        RadianceDirectParamsC* const A = args();
+        const float4 o = A->R.rays[2 * (size_t)ray], d = A->R.rays[2 * (size_t)ray + 1];
+        ro = xyz(o);
+        rd = xyz(d);
+        att = mk(1.0f, 1.0f, 1.0f);
+        acc = mk(0.0f, 0.0f, 0.0f);
+        prev_lamb = false;
+        depth = 0u;
+        rng.n = ((A->R.sample_base + sample) << 16) + 1u;
+        npaths++;
+        v3_start_trace<WIDE>(A->R.K.num_nodes, c, nrays);
+    };
+    const auto store = [&]() {
+        const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
+        RadianceDirectParamsC* const A = args();
+        const float ns = (float)A->R.samples;
+        if (A->R.sum) A->R.sum[ray] = make_float4(s.x, s.y, s.z, ns);
+        if (A->R.mean) {
+            const f3 m = divs_rn(s, ns, recip_in_range(ns));  // write_pixel's division
+            A->R.mean[ray] = make_float4(m.x, m.y, m.z, 1.0f);
+        }
+        c.mode = MODE_NEED;
+    };
+    const auto start = [&](uint32_t i) {
+        RadianceDirectParamsC* const A = args();
+        ray = i;
+        rng.pix = A->R.stream_ids ? A->R.stream_ids[i] : A->R.stream_base + i;
+        q0 = q1 = q2 = 0u;
+        sample = 0u;
+        if (A->R.K.max_depth != 0u) {
+            begin_path();
+        } else {  // exceeded recursion at once (Kernel.cu:79): every sample is 0, nothing is traced
+            npaths += A->R.samples;
+            c.mode = MODE_ENDED;
+        }
+    };
+    if (lane < count) start(ray);
+    uint32_t taken = 64u;  // wave-uniform: rays of the wave's range handed out so far
+    while (__ballot(c.mode != MODE_DONE) != 0) {
+        if (c.mode == MODE_TRAV) {
+            uint32_t thr = P->regen_threshold;
+            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
+            // (each call sees the tracing lanes of its state only: it leaves once a quarter of them have finished)
+            if (!shadow) {
+                const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
+                v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, ts, ro, rd, c, cnt,
+                                                                    64u, P->leaf_break);
+            }
+            if (shadow && c.mode == MODE_TRAV) {
+                const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
+                v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false, true>(nrsrc, P->nodes48, P->refs, P->prims, stk, ts, ro, rd, c,
+                                                                         cnt, 64u, P->leaf_break, 1e-4f);
+            }
+        }
+        if (c.mode == MODE_SHADE) {
+            KParamsC* const q = kparams_reload();
+            RadianceDirectParamsC* const dq = (RadianceDirectParamsC*)q;  // the light fields: loaded where they are used
+            if (shadow) {  // the shadow ray's answer, then the vertex's bounce ray
+                if (c.hit < 0) acc = add(acc, pend);
+                shadow = false;
+                rd = bd;
+                v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+            } else {
+                if (COUNT_TESTS) cnt.wshade += wave_leader();
+                f3 contrib;
+                ShadeVertex vx;
+                const int res = shade<true, false, false, true>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att,
+                                                                rng, rtl, contrib, nullptr, &vx);
+                bool ended = res == SHADE_ENDED;
+                // a sampled light after a Lambertian scatter: counted at that vertex
+                if (vx.mtype == RT_DIFFUSELIGHT && prev_lamb && dq->light_flags[c.hit] != 0u) contrib = mk(0.0f, 0.0f, 0.0f);
+                if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
+                    ended = true;
+                    contrib = mk(0.0f, 0.0f, 0.0f);
+                }
+                if (!ended) {
+                    prev_lamb = vx.mtype == RT_LAMBERTIAN;
+                    if (prev_lamb) {  // (vertex j = depth - 1, and j + 1 < max_depth; att is T · a already)
+                        philox_block(rng, ((dq->R.sample_base + sample) << 16) + 65536u - depth);
+                        f3 v, D;
+                        shadow = light_connection(q, dq->lights, dq->num_lights, philox_to_uniform(rng.r0), philox_to_uniform(rng.r1),
+                                                  philox_to_uniform(rng.r2), ro, vx.normal, v, D);
+                        if (shadow) {
+                            pend = mulv(att, D);
+                            bd = rd;
+                            rd = v;
+                        }
+                    }
+                    v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+                    if (shadow) c.t_best = 0.9999f;  // the range's upper end: read by the traversal, never written
+                } else {
+                    contrib = add(acc, contrib);
+                    q0 = sat_add(q0, quant12(contrib.x));
+                    q1 = sat_add(q1, quant12(contrib.y));
+                    q2 = sat_add(q2, quant12(contrib.z));
+                    if (++sample < dq->R.samples) begin_path();
+                    else c.mode = MODE_ENDED;
+                }
+            }
+        }
+        if (c.mode == MODE_ENDED) store();
+        const uint64_t needm = __ballot(c.mode == MODE_NEED);
+        if (needm != 0) {
+            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
+            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
+            if (c.mode == MODE_NEED) {
+                if (k < count) start(base + k);
+                else c.mode = MODE_DONE;
+            }
+        }
+    }
+    cnt.rays = nrays;
+    cnt.primary = npaths;
+    flush_counts<COUNT_TESTS>(*P, cnt);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The extra samples of a pixel list, traced and merged (rt_adaptive_samples): radiance_rays_kernel's schedule with list
 // entries as work items.  A lane owns entry i — pixel pixels[i], k_i paths — from its first camera ray to its merge.
 // Path j is the pixel's sample s = sample_base + j: camera_ray draws the jitter from block 0 of the sample's window
@@ -5616,7 +5844,10 @@ int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* a, rt_stream
         return RT_ERR_INVALID_ARGUMENT;
     };
     if (!a) return bad("NULL args");
-    if ((a->flags & ~(uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT) != 0) return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT");
+    if ((a->flags & ~((uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT | RT_RADIANCE_DIRECT_LIGHT)) != 0)
+        return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT and RT_RADIANCE_DIRECT_LIGHT");
+    const bool direct = (a->flags & RT_RADIANCE_DIRECT_LIGHT) != 0;
+    if (direct && a->max_depth > 4096u) return bad("max_depth above 4096 with RT_RADIANCE_DIRECT_LIGHT");
     if (a->reserved[0] != 0 || a->reserved[1] != 0 || a->reserved[2] != 0) return bad("reserved must be 0");
     if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
     if (a->count_tests > 1u) return bad("count_tests must be 0 or 1");
@@ -5640,8 +5871,9 @@ int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* a, rt_stream
     const DeviceScene& S = scene->dev;
     const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
     if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_radiance_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
-    dev::RadianceParams Q;
-    std::memset(&Q, 0, sizeof(Q));
+    dev::RadianceDirectParams DQ;
+    std::memset(&DQ, 0, sizeof(DQ));
+    dev::RadianceParams& Q = DQ.R;
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
     P.counters = (unsigned long long*)a->counters;
@@ -5669,6 +5901,15 @@ int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* a, rt_stream
     const uint32_t grid = (uint32_t)((n + Q.per_wave - 1) / Q.per_wave);
     hipStream_t s = (hipStream_t)stream;
     (void)hipGetLastError();
+    if (direct && S.num_lights != 0u) {  // (without a sampled light the flagged call is the flagless one)
+        DQ.lights = (const float4*)S.light_table;
+        DQ.light_flags = (const uint32_t*)S.light_table + (size_t)S.num_rects * 8u;
+        DQ.num_lights = S.num_lights;
+        const auto dkernel = S.wide_refs ? (a->count_tests ? dev::radiance_direct_kernel<true, true> : dev::radiance_direct_kernel<false, true>)
+                                         : (a->count_tests ? dev::radiance_direct_kernel<true, false> : dev::radiance_direct_kernel<false, false>);
+        hipLaunchKernelGGL(dkernel, dim3(grid), dim3(64), lds, s, DQ);
+        return hip_check(hipGetLastError(), "rt_radiance_rays: kernel launch", RT_ERR_LAUNCH);
+    }
     const auto kernel = S.wide_refs ? (a->count_tests ? dev::radiance_rays_kernel<true, true> : dev::radiance_rays_kernel<false, true>)
                                     : (a->count_tests ? dev::radiance_rays_kernel<true, false> : dev::radiance_rays_kernel<false, false>);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);

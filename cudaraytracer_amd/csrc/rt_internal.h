@@ -103,7 +103,20 @@ struct HostScene {
     uint32_t num_class_nodes = 0;         // form 2: chain nodes behind the num_chain_nodes ones in nodes48 / refs
     std::vector<uint32_t> class_records;  // 4 words per (leaf record, class): record r's class c at (r * 25 + c) * 4
     std::vector<double> class_regions;    // per leaf record its region: lo.xyz, hi.xyz (lo > hi: no cell names it)
+    // Light sampling (rt_radiance_rays, RT_RADIANCE_DIRECT_LIGHT).  `rects`: every active rectangle in ascending order
+    // of its index in the description, 8 words each: (centre.xyz, width), (height, bits(BVH-order primitive index),
+    // bits(material), bits(description index)) — what a material edit re-derives the list from.  `lights`: the
+    // description indices of the sampled lights, ascending.  `light_table` (uploaded; empty without a rectangle): 8
+    // words per rectangle, of which the first lights.size() are the lights in list order — (centre.xyz, width),
+    // (height, bits(primitive index), 0, 0) — then one word per primitive, 1 = a sampled light.
+    std::vector<uint32_t> rects;
+    std::vector<uint32_t> lights;
+    std::vector<uint32_t> light_table;
 };
+
+// lights and light_table of `h` from its rects, mats and num_prims (build_host_scene, rt_scene_update_materials: the
+// table keeps its size whatever the materials are).
+void build_light_table(HostScene* h);
 
 // rt_set_bounce_classes: the form build_host_scene builds (thread-local), and the node count at which form 2 falls
 // back to form 1 (real + chain + class nodes must stay below it; lowered by rt_bounce_class_entries_host for tests).

@@ -29,6 +29,8 @@ struct DeviceScene {
     const void* class_records = nullptr; // ... uint4 per (leaf record, direction class), or NULL (rt_set_bounce_classes)
     uint32_t grid_dim[3] = {0u, 0u, 0u};
     float grid_inv[3] = {0.0f, 0.0f, 0.0f}, grid_off[3] = {0.0f, 0.0f, 0.0f};
+    const void* light_table = nullptr;  // HostScene::light_table (NULL without a rectangle); num_rects and num_lights
+    uint32_t num_rects = 0, num_lights = 0;  // ... say where its per-primitive words begin and how many lights it lists
     const void* mats = nullptr;    // float4 × 3 per material
     const void* imgs = nullptr;    // int4 per image
     const void* texels = nullptr;  // RGB8

@@ -747,6 +747,27 @@ int pack_materials(const rt_material_desc* mats, uint32_t n, uint32_t num_images
     return RT_OK;
 }
 
+void build_light_table(HostScene* h) {
+    h->lights.clear();
+    h->light_table.clear();
+    const size_t nr = h->rects.size() / 8;
+    if (nr == 0) return;
+    h->light_table.assign(nr * 8 + std::max(h->num_prims, 1u), 0u);
+    uint32_t* const flag = h->light_table.data() + nr * 8;
+    for (size_t r = 0; r < nr; r++) {
+        const uint32_t* e = h->rects.data() + r * 8;
+        const float width = bits_to_float(e[3]), height = bits_to_float(e[4]);
+        const float* m0 = h->mats.data() + (size_t)e[6] * 12;
+        uint32_t mword;
+        std::memcpy(&mword, m0, 4);
+        if (!(width > 0.0f) || !(height > 0.0f) || (mword & 15u) != (uint32_t)RT_DIFFUSELIGHT || !(m0[2] > 0.0f)) continue;
+        uint32_t* o = h->light_table.data() + h->lights.size() * 8;
+        for (int k = 0; k < 6; k++) o[k] = e[k];
+        flag[e[5]] = 1u;
+        h->lights.push_back(e[7]);
+    }
+}
+
 int build_host_scene(const rt_scene_desc* desc, HostScene* out, std::string* err, bool with_texels) {
     if (!desc) { *err = "scene description is NULL"; return RT_ERR_INVALID_ARGUMENT; }
     if ((desc->num_hittables && !desc->hittables) || (desc->num_materials && !desc->materials) ||
@@ -913,6 +934,24 @@ int build_host_scene(const rt_scene_desc* desc, HostScene* out, std::string* err
     for (uint32_t i = 0; i < out->num_prims; i++) {
         out->prim_source[i] = B.prims[B.order[i]].src;
         pack_prim(desc->hittables[out->prim_source[i]], out->prims.data() + (size_t)i * 8);
+    }
+    {  // the active rectangles in list order, and from them the sampled lights (build_light_table)
+        std::vector<int> bvh_index(desc->num_hittables, -1);
+        for (uint32_t i = 0; i < out->num_prims; i++) bvh_index[out->prim_source[i]] = (int)i;
+        for (uint32_t i = 0; i < desc->num_hittables; i++) {
+            const rt_hittable_desc& h = desc->hittables[i];
+            if (bvh_index[i] < 0 || h.type == RT_SPHERE) continue;
+            const float f[5] = {h.center[0], h.center[1], h.center[2], h.width, h.height};
+            for (const float v : f) {
+                uint32_t w;
+                std::memcpy(&w, &v, 4);
+                out->rects.push_back(w);
+            }
+            out->rects.push_back((uint32_t)bvh_index[i]);
+            out->rects.push_back((uint32_t)h.material);
+            out->rects.push_back(i);
+        }
+        build_light_table(out);
     }
     if (out->num_prims == 0) return RT_OK;
     // The reference's own BVH (its boxes and shape, Hittable.cuh:303-385) over the active primitives in list order.

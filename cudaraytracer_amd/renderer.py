@@ -114,7 +114,7 @@ class DeviceScene:
 
     def radiance(self, rays, samples: int = 1, depth: int = 8, sample_base: int = 0, stream_ids=None, seed: int = 1984,
                  frame: int = 0, background=((1.0, 1.0, 1.0), (0.5, 0.7, 1.0)), mean: bool = True, rays_per_lane: int = 0,
-                 left_to_right: bool = False):
+                 left_to_right: bool = False, direct_light: bool = False):
         """Path-traced radiance along rays of the caller's own (rt_radiance_rays), asynchronous on torch's current
         stream.  rays: (n, 2, 4) float32, (origin, -), (direction, -) per ray — a torch tensor on the device, or a numpy
         array (uploaded to the current device).  Ray i takes `samples` paths of at most `depth` bounces on the Philox
@@ -122,7 +122,9 @@ class DeviceScene:
         uint32 / int32 (n,) device tensor (the values' 32 bits are the ids), e.g. camera_rays' pixel_index.
         background: (start, end) of the sky's blend.  Returns a float32 (n, 4) tensor: mean=True (r, g, b, 1), the
         average of the samples; mean=False (r, g, b, samples), their fixed-point sum, which adds into an accumulation
-        buffer as a frame's samples do."""
+        buffer as a frame's samples do.  direct_light=True (RT_RADIANCE_DIRECT_LIGHT): every Lambertian vertex also
+        connects to a point sampled on one of the scene's light rectangles (scenes.scene_lights) with a shadow ray —
+        the same expectation with far less noise where the lights are small; depth is then at most 4096."""
         if isinstance(rays, np.ndarray):
             rays = torch.from_numpy(np.array(rays, dtype=np.float32, order="C")).cuda()  # (a copy: the caller's may be read-only)
         if rays.dtype != torch.float32 or rays.dim() != 3 or tuple(rays.shape[1:]) != (2, 4) or not rays.is_cuda:
@@ -145,7 +147,7 @@ class DeviceScene:
             if stream_ids is not None:
                 a.stream_ids = stream_ids.data_ptr()
             a.n, a.rays_per_lane, a.samples_per_ray, a.sample_base, a.max_depth = n, rays_per_lane, samples, sample_base, depth
-            a.flags = abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0
+            a.flags = (abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0) | (abi.RT_RADIANCE_DIRECT_LIGHT if direct_light else 0)
             a.rng_seed, a.rng_frame = seed, frame
             a.background_start[:] = [float(v) for v in background[0]]
             a.background_end[:] = [float(v) for v in background[1]]

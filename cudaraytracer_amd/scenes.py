@@ -90,6 +90,18 @@ def scene_motion(prev_scene, scene) -> np.ndarray:
     return table
 
 
+def scene_lights(scene: Scene) -> list:
+    """The sampled lights of a scene (rt_scene_lights_host, host only): the indices into scene.hittables of the active
+    rectangles with a positive width and height and a DiffuseLight material of positive intensity, ascending — the
+    list DeviceScene.radiance(direct_light=True) samples."""
+    desc = scene.desc()
+    count = C.c_uint32(0)
+    check(lib().rt_scene_lights_host(C.byref(desc), None, 0, C.byref(count)), "rt_scene_lights_host")
+    out = (C.c_uint32 * max(1, count.value))()
+    check(lib().rt_scene_lights_host(C.byref(desc), out, count.value, C.byref(count)), "rt_scene_lights_host")
+    return [int(out[i]) for i in range(count.value)]
+
+
 TEXTURE_EARTH, TEXTURE_MOON, TEXTURE_SUN = 0, 1, 2
 DEFAULT_TEXTURE_SIZE = (1024, 512)  # parity fixtures; BASELINE config 5 uses the reference's 8192x4096
 

@@ -189,7 +189,8 @@ const char* rt_version(void);
  * word or existing entry point keep the number: rt_set_bounce_entries, rt_bounce_entries_host, rt_bounce_entry_cells,
  * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays, rt_camera_rays, rt_radiance_rays,
  * rt_set_bounce_classes, rt_bounce_class_entries_host, rt_adaptive_select, rt_adaptive_select_scratch_bytes,
- * rt_adaptive_samples, rt_temporal_gradient, rt_history_adapt (a caller asks the library for them by name). */
+ * rt_adaptive_samples, rt_temporal_gradient, rt_history_adapt, RT_RADIANCE_DIRECT_LIGHT, rt_scene_lights_host (a caller
+ * asks the library for them by name). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
@@ -507,7 +508,7 @@ int rt_camera_rays(const rt_camera_rays_args* args, rt_stream stream);
  * one-sample calls; and neither output depends on rays_per_lane, on rt_set_tuning or on the call.
  * counters[0]: color() iterations (rays traced; a path at the depth limit ends with 0 and no trace), counters[3]:
  * n * samples_per_ray; with count_tests the box / primitive tests and wave iterations, as rt_trace_rays.
- * flags: 0 or RT_FLAG_RIUS_LEFT_TO_RIGHT.  background_start / background_end: the sky of Kernel.cu:41-44.  There is no
+ * flags: 0, RT_FLAG_RIUS_LEFT_TO_RIGHT, RT_RADIANCE_DIRECT_LIGHT (below) or both.  background_start / background_end: the sky of Kernel.cu:41-44.  There is no
  * XORWOW mode (a per-ray call has no per-ray state buffer).  d need not be normalised; rays with a zero or non-finite
  * component get an unspecified value and touch only the scene's tables and their own elements.
  * One asynchronous launch on `stream`; every element is written once, by the lane that traced the ray.
@@ -515,7 +516,33 @@ int rt_camera_rays(const rt_camera_rays_args* args, rt_stream stream);
  * n > 0, neither sum nor mean, rays_per_lane above 16, samples_per_ray = 0 or sample_base + samples_per_ray above
  * RT_PHILOX_MAX_SPP, count_tests other than 0 or 1 or 1 without counters, other flag bits, non-zero reserved words, an
  * output (counters included) that overlaps rays, stream_ids or another output.  n = 0: RT_OK.  max_depth = 0: sums of
- * 0.  An empty scene gives the sky for every ray.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED. */
+ * 0.  An empty scene gives the sky for every ray.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED.
+ *
+ * RT_RADIANCE_DIRECT_LIGHT (opt-in, combinable with RT_FLAG_RIUS_LEFT_TO_RIGHT): next-event estimation.  The sampled
+ * lights of a scene are its active RT_XYRECT / RT_XZRECT / RT_YZRECT hittables with width > 0, height > 0 and an
+ * RT_DIFFUSELIGHT material of light_intensity > 0, in ascending order of their index in rt_scene_desc.hittables
+ * (rt_scene_lights_host; N_L of them; the order depends on nothing else).  With N_L = 0 the call is the flagless call.
+ * Otherwise the path of sample s is the flagless path (the same draws from block W + 1 on, W = (sample_base + s) << 16,
+ * so the same vertices) with two changes:
+ *   1. At loop iteration j whose hit is Lambertian and j + 1 < max_depth, with P the hit point, n the HitRecord normal
+ *      as Scatter uses it, a the albedo texture value and T the attenuation before the vertex: xi0, xi1, xi2 = words 0,
+ *      1, 2 of block W + 65535 - j (converted as every uniform of the stream; the path's own draws do not shift);
+ *      l = min((uint)(xi0 * N_L), N_L - 1); y = the light's centre + (xi1 - 0.5) * width along its width axis +
+ *      (xi2 - 0.5) * height along its height axis (rt_hittable_desc's axes); v = y - P — each a separately rounded
+ *      binary32 multiply, add or subtract in that order; d2 = v.v, c = (n.v) / sqrt(d2), c' = |v_axis| / sqrt(d2) with
+ *      v_axis the component of v along the light's normal axis.  If c > 0, c' > 0 and rt_occluded_rays' any-hit test of
+ *      the ray (P, v) over (tmin, tmax) = (1e-4f, 0.9999f) accepts nothing, the sample gains T * a * D,
+ *      D = Le(y) * 2 c^3 c' * A * N_L / (pi * d2), A = width * height, Le(y) = light_intensity * the light's texture
+ *      value at y with the (u, v) a hit at y would record.  (2 cos^3 / pi is the density of the reference's Lambertian
+ *      direction normal + RandomInUnitSphere() about n, so the term's expectation is the brute-force one; the cut
+ *      segment ends — blockers within 1e-4 |v| of either end are not seen — are the estimator's only deviation.)
+ *   2. A hit on a sampled light at iteration j >= 1 whose previous vertex was a Lambertian scatter adds 0 instead of
+ *      its emission (the path still ends there).  Every other emitter hit — camera rays, hits after metal or glass, any
+ *      unsampled emitter such as a light sphere — keeps its emission.
+ * The sample is the float sum of its direct terms in vertex order plus the terminal term, quantised once; sum, mean,
+ * the k-samples rule and the independence of rays_per_lane / rt_set_tuning hold as above.  counters[0] also counts the
+ * shadow rays traced.  With the flag, max_depth > 4096 is RT_ERR_INVALID_ARGUMENT (the two draw regions stay apart). */
+#define RT_RADIANCE_DIRECT_LIGHT (1u << 8)
 typedef struct rt_radiance_args {
     const float* rays;          /* device, n x 2 float4: (origin.xyz, -), (direction.xyz, -) */
     const uint32_t* stream_ids; /* optional device uint32[n]: the Philox subsequence of each ray */
@@ -528,7 +555,7 @@ typedef struct rt_radiance_args {
     uint32_t sample_base;
     uint32_t max_depth;
     uint32_t count_tests;       /* 0 or 1 */
-    uint32_t flags;             /* 0 or RT_FLAG_RIUS_LEFT_TO_RIGHT */
+    uint32_t flags;             /* RT_FLAG_RIUS_LEFT_TO_RIGHT, RT_RADIANCE_DIRECT_LIGHT or both, or 0 */
     uint32_t stream_base;       /* without stream_ids: ray i draws from subsequence stream_base + i */
     uint64_t rng_seed;
     uint32_t rng_frame;
@@ -1137,6 +1164,11 @@ typedef struct rt_host_tables_info {
 } rt_host_tables_info;
 int rt_build_host_tables(const rt_scene_desc* desc, float* nodes, float* prims, float* materials,
                          int32_t* prim_source, rt_host_tables_info* info);
+
+/* The sampled lights of a scene (RT_RADIANCE_DIRECT_LIGHT's list, rt_radiance_rays): rt_scene_create's validation, then
+ * *count = N_L and the first min(N_L, capacity) indices into desc->hittables, ascending.  hittables may be NULL when
+ * capacity is 0.  Independent of the BVH and of rt_set_tuning. */
+int rt_scene_lights_host(const rt_scene_desc* desc, uint32_t* hittables, uint32_t capacity, uint32_t* count);
 
 /* The v3 kernels' per-tile entry records, computed on the host by the classifier the device pre-pass runs: for tiles
  * first_tile .. first_tile + num_tiles - 1 (8x8 tiles, row-major over ceil(width / 8) columns of the rank's local

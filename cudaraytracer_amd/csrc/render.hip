@@ -2679,9 +2679,132 @@ __global__ __launch_bounds__(64, WAVES_PER_SIMD) void render_kernel_v3(const KPa
     finish_pixel<COUNT_TESTS>(P, pix, state_at(P, pix), rng, col, cnt);
 }
 
-// Closest hit of a batch of rays (rt_trace_rays): v3's traversal (while-while, postponed leaves, the regeneration
-// threshold and leaf-break rules) without the shading — a wave owns `per_wave` consecutive rays of the batch and a
-// lane whose ray is done takes the wave's next one (ballot + mbcnt on a wave-uniform counter).  Rays are
+// ---------------------------------------------------------------------------------------------------
+// The per-ray kernels (trace, query, occlusion, radiance, direct light, adaptive samples, temporal gradient) share three
+// pieces: RayWave, a wave's traversal state; ray_wave_run, the schedule; SampleSums / path_vertex, the path step.
+//
+// The schedule: a wave owns `count` consecutive work items from `base` — rays of a batch, list entries, strata — and runs
+// v3's traversal (while-while, postponed leaves, the regeneration threshold and leaf-break rules) on them.  A lane whose
+// item is done takes the wave's next one (ballot + mbcnt on a wave-uniform counter), so which lane traces which item
+// depends on the traversals' lengths; every kernel writes an item's outputs from the lane that owns it and from that
+// item's data alone, which is why no result depends on the schedule.
+// query_rays_kernel and occlusion_rays_kernel run the same schedule from copies of their own: they measured slower on
+// the shared pieces.  A change to the schedule goes into ray_wave_run and into those two.
+// ---------------------------------------------------------------------------------------------------
+template <bool WIDE>
+struct RayWave {
+    using Entry = typename RefW<WIDE>::Entry;
+    Entry* stk;  // the lane's stack in the launch's dynamic LDS ((depth + 2) levels of 64 entries)
+    __amdgpu_buffer_rsrc_t nrsrc;
+    Counts cnt;
+    Cursor c;
+    uint32_t nrays;
+    f3 ro, rd;
+
+    __device__ __forceinline__ void begin(const KParams* P) {
+        extern __shared__ float4 lds[];
+        stk = reinterpret_cast<Entry*>(lds) + (threadIdx.x & 63u);
+        nrsrc = __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
+        stk[0] = (Entry)RefW<WIDE>::kSentinel;
+        stk[64] = (Entry)RefW<WIDE>::kSentinel;
+        cnt = Counts{0, 0, 0, 0, 0, 0, 0};
+        c = Cursor{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
+        nrays = 0u;
+        ro = rd = mk(0.0f, 0.0f, 0.0f);
+    }
+    // the wave's diagnostic counts (npaths: the paths its lanes began)
+    template <bool COUNT_TESTS>
+    __device__ __forceinline__ void finish(const KParams& P, const uint32_t npaths) {
+        cnt.rays = nrays;
+        cnt.primary = npaths;
+        flush_counts<COUNT_TESTS>(P, cnt);
+    }
+};
+
+// Items of the wave at `base` when every wave takes `per_wave` of `n` (the grid covers n: base < n; base + per_wave may wrap).
+__device__ __forceinline__ uint32_t wave_items(const uint32_t n, const uint32_t base, const uint32_t per_wave) {
+    return min(n - base, per_wave);
+}
+
+// The work-list loop over items [base, base + count).  start(i): the lane takes item i (it leaves the lane in MODE_TRAV,
+// or in MODE_SHADE / MODE_ENDED / MODE_NEED where nothing is traced).  step(): run after the traversal; it handles
+// MODE_SHADE and MODE_ENDED and leaves the lane in MODE_TRAV (the path goes on), MODE_NEED (the item is stored) or
+// MODE_ENDED.  trav(thr): the traversal of the lanes in MODE_TRAV, `thr` the number of tracing lanes below which it
+// returns.  P is read where it is used (the loop holds nothing of it).
+template <bool WIDE, class Start, class Step, class Trav>
+__device__ __forceinline__ void ray_wave_run(const KParams* P, RayWave<WIDE>& w, const uint32_t base, const uint32_t count,
+                                             const Start& start, const Step& step, const Trav& trav) {
+    Cursor& c = w.c;
+    if ((threadIdx.x & 63u) < count) start(base + (threadIdx.x & 63u));
+    uint32_t taken = 64u;  // wave-uniform: items of the wave's range handed out so far
+    while (__ballot(c.mode != MODE_DONE) != 0) {
+        if (c.mode == MODE_TRAV) {
+            uint32_t thr = P->regen_threshold;
+            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
+            trav(thr);
+        }
+        step();
+        const uint64_t needm = __ballot(c.mode == MODE_NEED);
+        if (needm != 0) {
+            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
+            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088 beyond the turns of items that trace nothing)
+            if (c.mode == MODE_NEED) {
+                if (k < count) start(base + k);
+                else c.mode = MODE_DONE;
+            }
+        }
+    }
+}
+
+// ... with the closest-hit traversal from the root
+template <bool COUNT_TESTS, bool WIDE, class Start, class Step>
+__device__ __forceinline__ void ray_wave_run(const KParams* P, RayWave<WIDE>& w, const uint32_t base, const uint32_t count,
+                                             const Start& start, const Step& step) {
+    ray_wave_run(P, w, base, count, start, step, [&](const uint32_t thr) {
+        v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(w.nrsrc, P->nodes48, P->refs, P->prims, w.stk, thr, w.ro, w.rd, w.c,
+                                                            w.cnt, 64u, P->leaf_break);
+    });
+}
+
+// An item's sample sums, 2^-12 units per channel, saturating: order-free (add_sample's, for RngPhilox).
+struct SampleSums {
+    uint32_t q0, q1, q2;
+    static __device__ __forceinline__ SampleSums of(const f3 contrib) {  // one sample, quantised
+        return SampleSums{quant12(contrib.x), quant12(contrib.y), quant12(contrib.z)};
+    }
+    __device__ __forceinline__ void add(const SampleSums s) {
+        q0 = sat_add(q0, s.q0);
+        q1 = sat_add(q1, s.q1);
+        q2 = sat_add(q2, s.q2);
+    }
+    __device__ __forceinline__ void add(const f3 contrib) { add(of(contrib)); }
+    __device__ __forceinline__ f3 sum() const {  // pixel_sum's conversion
+        return mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));
+    }
+    __device__ __forceinline__ f3 mean(const float ns) const {  // write_pixel's division
+        return divs_rn(sum(), ns, recip_in_range(ns));
+    }
+};
+
+// color()'s bounce loop, one vertex per call: shades the lane's closest hit on its Philox stream and applies the depth
+// rule.  True: the path ended with `contrib`; false: its next ray is under way from the root (MODE_TRAV).
+template <bool COUNT_TESTS, bool WIDE>
+__device__ __forceinline__ bool path_vertex(RayWave<WIDE>& w, f3& att, RngPhilox& rng, const bool rtl, uint32_t& depth,
+                                            f3& contrib) {
+    if (COUNT_TESTS) w.cnt.wshade += wave_leader();
+    KParamsC* const q = kparams_reload();
+    const int res = shade<true, false, false>(q, q->prims, q->mats, q->imgs, w.c.hit, w.c.tag, w.c.t_best, w.ro, w.rd, att, rng,
+                                              rtl, contrib);
+    bool ended = res == SHADE_ENDED;
+    if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
+        ended = true;
+        contrib = mk(0.0f, 0.0f, 0.0f);
+    }
+    if (!ended) v3_start_trace<WIDE>(q->num_nodes, w.c, w.nrays);
+    return ended;
+}
+
+// Closest hit of a batch of rays (rt_trace_rays): the schedule alone, no shading.  Rays are
 // (origin, -), (direction, -) float4 pairs; out[i] = (primitive index in the scene's BVH order or -1, t bits).
 // WIDE: the build for scenes with 32-bit references (RefW).
 // For measuring how ray order changes traversal cost (tools/coherence.py: a frame's bounce-2 rays in generation
@@ -2690,55 +2813,26 @@ template <bool COUNT_TESTS, bool WIDE = false>
 __global__ __launch_bounds__(64, 8) void trace_rays_kernel(const KParams P, const float4* __restrict__ rays,
                                                           const uint32_t n_rays, const uint32_t per_wave,
                                                           int2* __restrict__ out) {
-    using Entry = typename RefW<WIDE>::Entry;
-    extern __shared__ float4 lds[];
-    const uint32_t lane = threadIdx.x & 63u;
-    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
-    const __amdgpu_buffer_rsrc_t nrsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)P.nodes48, (short)0, (int)(P.num_nodes * 48u), 0x00020000);
-    stk[0] = (Entry)RefW<WIDE>::kSentinel;
-    stk[64] = (Entry)RefW<WIDE>::kSentinel;
+    RayWave<WIDE> w;
+    w.begin(&P);
+    Cursor& c = w.c;
     const uint32_t base = blockIdx.x * per_wave;
-    const uint32_t end = min(base + per_wave, n_rays);
-    Counts cnt{0, 0, 0, 0, 0, 0, 0};
-    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
-    uint32_t ray = base + lane, nrays = 0u;
-    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro;
+    uint32_t ray = 0u;
     const auto start = [&](uint32_t i) {
+        ray = i;
         const float4 o = rays[2 * (size_t)i], d = rays[2 * (size_t)i + 1];
-        ro = xyz(o);
-        rd = xyz(d);
-        v3_start_trace<WIDE>(P.num_nodes, c, nrays);
+        w.ro = xyz(o);
+        w.rd = xyz(d);
+        v3_start_trace<WIDE>(P.num_nodes, c, w.nrays);
     };
-    if (ray < end) start(ray);
-    uint32_t next = base + 64u;  // wave-uniform
-    while (__ballot(c.mode != MODE_DONE) != 0) {
-        if (c.mode == MODE_TRAV) {
-            uint32_t thr = P.regen_threshold;
-            if (P.regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P.regen_live_frac) >> 6);
-            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P.nodes48, P.refs, P.prims, stk, thr, ro, rd, c, cnt, 64u,
-                                                           P.leaf_break);
-        }
+    const auto step = [&]() {
         if (c.mode == MODE_SHADE) {
             out[ray] = make_int2(c.hit, __float_as_int(c.t_best));
             c.mode = MODE_NEED;
         }
-        const uint64_t needm = __ballot(c.mode == MODE_NEED);
-        if (needm != 0) {
-            const uint32_t i = next + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
-            next += (uint32_t)__popcll(needm);
-            if (c.mode == MODE_NEED) {
-                if (i < end) {
-                    ray = i;
-                    start(i);
-                } else {
-                    c.mode = MODE_DONE;
-                }
-            }
-        }
-    }
-    cnt.rays = nrays;
-    flush_counts<COUNT_TESTS>(P, cnt);
+    };
+    ray_wave_run<COUNT_TESTS>(&P, w, base, wave_items(n_rays, base, per_wave), start, step);
+    w.template finish<COUNT_TESTS>(P, 0u);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -3982,10 +4076,10 @@ __global__ __launch_bounds__(64, 4) void gbuffer_kernel(const GBufParams G) {
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Ray queries with hit records (rt_query_rays): trace_rays_kernel's schedule — a wave owns `per_wave` consecutive rays
-// of the caller's batch, a lane whose ray is done writes its record and takes the wave's next one (ballot + mbcnt on
-// a wave-uniform counter) — with rt_gbuffer's record (first_hit_record) per ray.  Every output is optional; each
-// element is written by the one lane that traced the ray, so the result does not depend on the schedule.
+// Ray queries with hit records (rt_query_rays): ray_wave_run's schedule over the caller's batch, with rt_gbuffer's record
+// (first_hit_record) per ray.  Every output is optional; each element is written by the one lane that traced the ray,
+// so the result does not depend on the schedule.  The kernel keeps a copy of the set-up and the loop: on the shared
+// pieces its WIDE build measured 3.5 % slower on the 9 001-sphere field.
 // ---------------------------------------------------------------------------------------------------
 struct QueryParams {
     KParams K;
@@ -4076,8 +4170,8 @@ __global__ __launch_bounds__(64, 4) void query_rays_kernel(const QueryParams Q) 
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Any-hit visibility queries with a range per ray (rt_occluded_rays): query_rays_kernel's schedule with v3_traverse's
-// ANYHIT mode.  rays[2i] = (origin, tmin), rays[2i + 1] = (direction, tmax); a ray with !(tmin <= tmax) goes to its
+// Any-hit visibility queries with a range per ray (rt_occluded_rays): ray_wave_run's schedule with v3_traverse's ANYHIT
+// mode as its traversal, in a copy of its own (on the shared pieces it measured 2.5 % slower on C2).  rays[2i] = (origin, tmin), rays[2i + 1] = (direction, tmax); a ray with !(tmin <= tmax) goes to its
 // store without a traversal (and is not counted as a ray).  A lane writes its ray's byte / index itself, so the result
 // does not depend on the schedule; and since the range never shrinks, neither does the primitive that ends a traversal.
 // ---------------------------------------------------------------------------------------------------
@@ -4154,11 +4248,10 @@ __global__ __launch_bounds__(64, 4) void occlusion_rays_kernel(const OcclusionPa
 }
 
 // ---------------------------------------------------------------------------------------------------
-// Path-traced radiance per ray (rt_radiance_rays): query_rays_kernel's schedule with color()'s bounce loop in the
-// shading step.  A lane owns one ray of the batch for all its samples: MODE_SHADE calls shade() on the Philox stream
-// (key, subsequence id, frame); a path that continues restarts the traversal, one that ends goes into the lane's three
-// 2^-12 fixed-point sums, and the lane then reloads its own ray for the next sample or stores and takes the wave's
-// next ray.  Sample s of a ray draws from block ((sample_base + s) << 16) + 1 on: block 0 of the window is the camera
+// Path-traced radiance per ray (rt_radiance_rays): ray_wave_run with color()'s bounce loop (path_vertex) as its step.
+// A lane owns one ray of the batch for all its samples: MODE_SHADE shades on the Philox stream (key, subsequence id,
+// frame); a path that continues restarts the traversal, one that ends goes into the lane's SampleSums, and the lane
+// then reloads its own ray for the next sample or stores and takes the wave's next ray.  Sample s of a ray draws from block ((sample_base + s) << 16) + 1 on: block 0 of the window is the camera
 // jitter's (camera_ray), which rt_camera_rays reads.  The closest hit is the geometric one (rt_trace_rays' semantics);
 // the sums are order-free and every element is written by the lane that traced the ray, so the result does not depend
 // on the schedule.  The params begin with a KParams: shade() and philox_block() read the kernel arguments as one.
@@ -4176,42 +4269,34 @@ static_assert(offsetof(RadianceParams, K) == 0, "philox_block and kparams_reload
 
 template <bool COUNT_TESTS, bool WIDE>
 __global__ __launch_bounds__(64, 4) void radiance_rays_kernel(const RadianceParams Q) {
-    using Entry = typename RefW<WIDE>::Entry;
     const KParams* P = &Q.K;
-    extern __shared__ float4 lds[];
-    const uint32_t lane = threadIdx.x & 63u;
-    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
-    const __amdgpu_buffer_rsrc_t nrsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
-    stk[0] = (Entry)RefW<WIDE>::kSentinel;
-    stk[64] = (Entry)RefW<WIDE>::kSentinel;
-    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
-    const uint32_t count = min(Q.n - base, Q.per_wave);  // rays of this wave's range (base + per_wave may wrap)
-    Counts cnt{0, 0, 0, 0, 0, 0, 0};
-    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
-    uint32_t ray = base + lane, nrays = 0u, npaths = 0u;
-    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
-    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the ray's sample sums, 2^-12 units
+    RayWave<WIDE> w;
+    w.begin(P);
+    Cursor& c = w.c;
+    const uint32_t base = blockIdx.x * Q.per_wave;
+    uint32_t ray = 0u, npaths = 0u;
+    f3 att = mk(0.0f, 0.0f, 0.0f);
+    SampleSums sums{0u, 0u, 0u};  // the ray's
     uint32_t sample = 0u, depth = 0u;
     RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
     const bool rtl = P->rius_rtl != 0;
     // the lane's ray starts its path of sample `sample`
     const auto begin_path = [&]() {
         const float4 o = Q.rays[2 * (size_t)ray], d = Q.rays[2 * (size_t)ray + 1];
-        ro = xyz(o);
-        rd = xyz(d);
+        w.ro = xyz(o);
+        w.rd = xyz(d);
         att = mk(1.0f, 1.0f, 1.0f);
         depth = 0u;
         rng.n = ((Q.sample_base + sample) << 16) + 1u;
         npaths++;
-        v3_start_trace<WIDE>(P->num_nodes, c, nrays);
+        v3_start_trace<WIDE>(P->num_nodes, c, w.nrays);
     };
     const auto store = [&]() {
-        const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
+        const f3 s = sums.sum();
         const float ns = (float)Q.samples;
         if (Q.sum) Q.sum[ray] = make_float4(s.x, s.y, s.z, ns);
         if (Q.mean) {
-            const f3 m = divs_rn(s, ns, recip_in_range(ns));  // write_pixel's division
+            const f3 m = sums.mean(ns);
             Q.mean[ray] = make_float4(m.x, m.y, m.z, 1.0f);
         }
         c.mode = MODE_NEED;
@@ -4219,7 +4304,7 @@ __global__ __launch_bounds__(64, 4) void radiance_rays_kernel(const RadiancePara
     const auto start = [&](uint32_t i) {
         ray = i;
         rng.pix = Q.stream_ids ? Q.stream_ids[i] : Q.stream_base + i;
-        q0 = q1 = q2 = 0u;
+        sums = SampleSums{0u, 0u, 0u};
         sample = 0u;
         if (P->max_depth != 0u) {
             begin_path();
@@ -4228,55 +4313,23 @@ __global__ __launch_bounds__(64, 4) void radiance_rays_kernel(const RadiancePara
             c.mode = MODE_ENDED;
         }
     };
-    if (lane < count) start(ray);
-    uint32_t taken = 64u;  // wave-uniform: rays of the wave's range handed out so far
-    while (__ballot(c.mode != MODE_DONE) != 0) {
-        if (c.mode == MODE_TRAV) {
-            uint32_t thr = P->regen_threshold;
-            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
-            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c, cnt, 64u,
-                                                                P->leaf_break);
-        }
-        if (c.mode == MODE_SHADE) {
-            if (COUNT_TESTS) cnt.wshade += wave_leader();
-            KParamsC* const q = kparams_reload();
-            f3 contrib;
-            const int res = shade<true, false, false>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att, rng, rtl,
-                                                      contrib);
-            bool ended = res == SHADE_ENDED;
-            if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
-                ended = true;
-                contrib = mk(0.0f, 0.0f, 0.0f);
-            }
-            if (!ended) {
-                v3_start_trace<WIDE>(q->num_nodes, c, nrays);
-            } else {
-                q0 = sat_add(q0, quant12(contrib.x));
-                q1 = sat_add(q1, quant12(contrib.y));
-                q2 = sat_add(q2, quant12(contrib.z));
-                if (++sample < Q.samples) begin_path();
-                else c.mode = MODE_ENDED;
-            }
+    const auto step = [&]() {
+        f3 contrib;
+        if (c.mode == MODE_SHADE && path_vertex<COUNT_TESTS>(w, att, rng, rtl, depth, contrib)) {
+            sums.add(contrib);
+            if (++sample < Q.samples) begin_path();
+            else c.mode = MODE_ENDED;
         }
         if (c.mode == MODE_ENDED) store();
-        const uint64_t needm = __ballot(c.mode == MODE_NEED);
-        if (needm != 0) {
-            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
-            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
-            if (c.mode == MODE_NEED) {
-                if (k < count) start(base + k);
-                else c.mode = MODE_DONE;
-            }
-        }
-    }
-    cnt.rays = nrays;
-    cnt.primary = npaths;
-    flush_counts<COUNT_TESTS>(*P, cnt);
+    };
+    ray_wave_run<COUNT_TESTS>(P, w, base, wave_items(Q.n, base, Q.per_wave), start, step);
+    w.template finish<COUNT_TESTS>(*P, npaths);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // rt_radiance_rays with RT_RADIANCE_DIRECT_LIGHT (next-event estimation; rt_hip.h has the definition, DESIGN.md §20 the
-// density argument): radiance_rays_kernel's schedule and path, where a lane whose path continues from a Lambertian
+// density argument): ray_wave_run with a traversal of its own and radiance_rays_kernel's path (SampleSums; the vertex
+// step is the kernel's own, around its shadow state), where a lane whose path continues from a Lambertian
 // vertex first traces a shadow ray to a point sampled on one of the scene's light rectangles — v3_traverse's ANYHIT
 // build over (1e-4, 0.9999) of the segment, as occlusion_rays_kernel runs it — and then its bounce ray, whose direction
 // waits in `bd`.  A wave's lanes are in either state at once: each traversal step runs the closest-hit lanes, then the
@@ -4346,28 +4399,22 @@ typedef __attribute__((address_space(4))) const RadianceDirectParams RadianceDir
 // (The counting builds carry both traversals' diagnostic counts: they ask for two waves per SIMD, not four.)
 template <bool COUNT_TESTS, bool WIDE>
 __global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kernel(const RadianceDirectParams DQ) {
-    using Entry = typename RefW<WIDE>::Entry;
     const RadianceParams& Q = DQ.R;
     const KParams* P = &Q.K;
-    extern __shared__ float4 lds[];
-    const uint32_t lane = threadIdx.x & 63u;
-    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
-    const __amdgpu_buffer_rsrc_t nrsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
-    stk[0] = (Entry)RefW<WIDE>::kSentinel;
-    stk[64] = (Entry)RefW<WIDE>::kSentinel;
-    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
-    const uint32_t count = min(Q.n - base, Q.per_wave);  // rays of this wave's range (base + per_wave may wrap)
-    Counts cnt{0, 0, 0, 0, 0, 0, 0};
-    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
-    uint32_t ray = base + lane, nrays = 0u, npaths = 0u;
-    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
-    f3 acc = ro;   // the path's direct terms so far
-    f3 pend = ro;  // shadow state: the term the shadow ray decides
-    f3 bd = ro;    // shadow state: the bounce ray's direction
+    RayWave<WIDE> w;
+    w.begin(P);
+    Cursor& c = w.c;
+    f3 &ro = w.ro, &rd = w.rd;
+    uint32_t& nrays = w.nrays;
+    const uint32_t base = blockIdx.x * Q.per_wave;
+    uint32_t ray = 0u, npaths = 0u;
+    f3 att = mk(0.0f, 0.0f, 0.0f);
+    f3 acc = att;   // the path's direct terms so far
+    f3 pend = att;  // shadow state: the term the shadow ray decides
+    f3 bd = att;    // shadow state: the bounce ray's direction
     bool shadow = false;     // the lane traces (or has traced) a shadow ray
     bool prev_lamb = false;  // the path's previous vertex was a Lambertian scatter
-    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the ray's sample sums, 2^-12 units
+    SampleSums sums{0u, 0u, 0u};  // the ray's
     uint32_t sample = 0u, depth = 0u;
     RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
     const bool rtl = P->rius_rtl != 0;
@@ -4375,6 +4422,9 @@ __global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kerne
     // (the call's own arguments are loaded where they are used, as shade() loads the scene's: held across the two
     // traversals they would not fit the scalar registers)
     const auto args = []() { return (RadianceDirectParamsC*)kparams_reload(); };
+    // (a first call above every branch: the kernel-argument pointer then has one definition that all later calls share;
+    // left to the branches, their copies meet in a per-lane phi, which kparams_reload's scalar constraint cannot take)
+    (void)args();
     const auto begin_path = [&]() {
         RadianceDirectParamsC* const A = args();
         const float4 o = A->R.rays[2 * (size_t)ray], d = A->R.rays[2 * (size_t)ray + 1];
@@ -4389,12 +4439,12 @@ __global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kerne
         v3_start_trace<WIDE>(A->R.K.num_nodes, c, nrays);
     };
     const auto store = [&]() {
-        const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
+        const f3 s = sums.sum();
         RadianceDirectParamsC* const A = args();
         const float ns = (float)A->R.samples;
         if (A->R.sum) A->R.sum[ray] = make_float4(s.x, s.y, s.z, ns);
         if (A->R.mean) {
-            const f3 m = divs_rn(s, ns, recip_in_range(ns));  // write_pixel's division
+            const f3 m = sums.mean(ns);
             A->R.mean[ray] = make_float4(m.x, m.y, m.z, 1.0f);
         }
         c.mode = MODE_NEED;
@@ -4403,7 +4453,7 @@ __global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kerne
         RadianceDirectParamsC* const A = args();
         ray = i;
         rng.pix = A->R.stream_ids ? A->R.stream_ids[i] : A->R.stream_base + i;
-        q0 = q1 = q2 = 0u;
+        sums = SampleSums{0u, 0u, 0u};
         sample = 0u;
         if (A->R.K.max_depth != 0u) {
             begin_path();
@@ -4412,24 +4462,23 @@ __global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kerne
             c.mode = MODE_ENDED;
         }
     };
-    if (lane < count) start(ray);
-    uint32_t taken = 64u;  // wave-uniform: rays of the wave's range handed out so far
-    while (__ballot(c.mode != MODE_DONE) != 0) {
-        if (c.mode == MODE_TRAV) {
-            uint32_t thr = P->regen_threshold;
-            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
-            // (each call sees the tracing lanes of its state only: it leaves once a quarter of them have finished)
-            if (!shadow) {
-                const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
-                v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, ts, ro, rd, c, cnt,
-                                                                    64u, P->leaf_break);
-            }
-            if (shadow && c.mode == MODE_TRAV) {
-                const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
-                v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false, true>(nrsrc, P->nodes48, P->refs, P->prims, stk, ts, ro, rd, c,
-                                                                         cnt, 64u, P->leaf_break, 1e-4f);
-            }
+    // closest-hit lanes, then shadow lanes
+    // (each call sees the tracing lanes of its state only: it leaves once a quarter of them have finished)
+    const auto trav = [&](const uint32_t thr) {
+        if (!shadow) {
+            const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(w.nrsrc, P->nodes48, P->refs, P->prims, w.stk, ts, ro, rd, c, w.cnt,
+                                                                64u, P->leaf_break);
         }
+        if (shadow && c.mode == MODE_TRAV) {
+            const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false, true>(w.nrsrc, P->nodes48, P->refs, P->prims, w.stk, ts, ro, rd, c,
+                                                                     w.cnt, 64u, P->leaf_break, 1e-4f);
+        }
+    };
+    // path_vertex's step around the shadow state: shade() with its VERTEX record, the sampled light's rule between the
+    // shading and the depth rule, and the connection before the bounce ray starts
+    const auto step = [&]() {
         if (c.mode == MODE_SHADE) {
             KParamsC* const q = kparams_reload();
             RadianceDirectParamsC* const dq = (RadianceDirectParamsC*)q;  // the light fields: loaded where they are used
@@ -4439,7 +4488,7 @@ __global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kerne
                 rd = bd;
                 v3_start_trace<WIDE>(q->num_nodes, c, nrays);
             } else {
-                if (COUNT_TESTS) cnt.wshade += wave_leader();
+                if (COUNT_TESTS) w.cnt.wshade += wave_leader();
                 f3 contrib;
                 ShadeVertex vx;
                 const int res = shade<true, false, false, true>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att,
@@ -4467,33 +4516,20 @@ __global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void radiance_direct_kerne
                     v3_start_trace<WIDE>(q->num_nodes, c, nrays);
                     if (shadow) c.t_best = 0.9999f;  // the range's upper end: read by the traversal, never written
                 } else {
-                    contrib = add(acc, contrib);
-                    q0 = sat_add(q0, quant12(contrib.x));
-                    q1 = sat_add(q1, quant12(contrib.y));
-                    q2 = sat_add(q2, quant12(contrib.z));
+                    sums.add(add(acc, contrib));
                     if (++sample < dq->R.samples) begin_path();
                     else c.mode = MODE_ENDED;
                 }
             }
         }
         if (c.mode == MODE_ENDED) store();
-        const uint64_t needm = __ballot(c.mode == MODE_NEED);
-        if (needm != 0) {
-            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
-            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
-            if (c.mode == MODE_NEED) {
-                if (k < count) start(base + k);
-                else c.mode = MODE_DONE;
-            }
-        }
-    }
-    cnt.rays = nrays;
-    cnt.primary = npaths;
-    flush_counts<COUNT_TESTS>(*P, cnt);
+    };
+    ray_wave_run(P, w, base, wave_items(Q.n, base, Q.per_wave), start, step, trav);
+    w.template finish<COUNT_TESTS>(*P, npaths);
 }
 
 // ---------------------------------------------------------------------------------------------------
-// The extra samples of a pixel list, traced and merged (rt_adaptive_samples): radiance_rays_kernel's schedule with list
+// The extra samples of a pixel list, traced and merged (rt_adaptive_samples): ray_wave_run and path_vertex with list
 // entries as work items.  A lane owns entry i — pixel pixels[i], k_i paths — from its first camera ray to its merge.
 // Path j is the pixel's sample s = sample_base + j: camera_ray draws the jitter from block 0 of the sample's window
 // (lane_camera and camera_ray as the render kernels call them, so no ray batch exists in memory and every path has its
@@ -4520,25 +4556,17 @@ static_assert(offsetof(AdaptiveParams, K) == 0, "philox_block and kparams_reload
 
 template <bool COUNT_TESTS, bool WIDE>
 __global__ __launch_bounds__(64, 4) void adaptive_samples_kernel(const AdaptiveParams Q) {
-    using Entry = typename RefW<WIDE>::Entry;
     const KParams* P = &Q.K;
-    extern __shared__ float4 lds[];
-    const uint32_t lane = threadIdx.x & 63u;
     const uint32_t entries = Q.count ? min(Q.count[0], Q.capacity) : Q.capacity;  // (wave-uniform)
     const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers capacity: base < capacity)
     if (base >= entries) return;
-    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
-    const __amdgpu_buffer_rsrc_t nrsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
-    stk[0] = (Entry)RefW<WIDE>::kSentinel;
-    stk[64] = (Entry)RefW<WIDE>::kSentinel;
-    const uint32_t count = min(entries - base, Q.per_wave);  // entries of this wave's range
-    const uint32_t frame_pixels = P->width * P->height;      // (below 2^31: checked on the host)
-    Counts cnt{0, 0, 0, 0, 0, 0, 0};
-    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
-    uint32_t nrays = 0u, npaths = 0u;
-    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
-    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the entry's sample sums, 2^-12 units (the accumulation plane's)
+    RayWave<WIDE> w;
+    w.begin(P);
+    Cursor& c = w.c;
+    const uint32_t frame_pixels = P->width * P->height;  // (below 2^31: checked on the host)
+    uint32_t npaths = 0u;
+    f3 att = mk(0.0f, 0.0f, 0.0f);
+    SampleSums sums{0u, 0u, 0u};  // the entry's (the accumulation plane's)
     float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the pixel's history and moments while the lane owns it
     float2 mo = make_float2(0.0f, 0.0f);
     uint32_t pixel = 0u, paths = 0u, sample = 0u, depth = 0u;
@@ -4548,19 +4576,18 @@ __global__ __launch_bounds__(64, 4) void adaptive_samples_kernel(const AdaptiveP
     const auto begin_path = [&]() {
         KParamsC* const q = kparams_reload();
         const uint32_t g = pixel / q->width, x = pixel - g * q->width;
-        camera_ray(q, lane_camera(q, x, g), rng, ro, rd, Q.sample_base + sample);
+        camera_ray(q, lane_camera(q, x, g), rng, w.ro, w.rd, Q.sample_base + sample);
         att = mk(1.0f, 1.0f, 1.0f);
         depth = 0u;
         npaths++;
-        v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+        v3_start_trace<WIDE>(q->num_nodes, c, w.nrays);
     };
-    // a path ended with these 2^-12 units per channel: one more frame's blend, and the entry's sum
-    const auto merge = [&](const uint32_t u0, const uint32_t u1, const uint32_t u2) {
-        q0 = sat_add(q0, u0);
-        q1 = sat_add(q1, u1);
-        q2 = sat_add(q2, u2);
+    // a path ended with this contribution: the entry's sum, and one more frame's blend of its 2^-12 units
+    const auto merge = [&](const f3 contrib) {
+        const SampleSums one = SampleSums::of(contrib);
+        sums.add(one);
         if (Q.history) {
-            const f3 cs = mk((float)u0 * (1.0f / 4096.0f), (float)u1 * (1.0f / 4096.0f), (float)u2 * (1.0f / 4096.0f));
+            const f3 cs = one.sum();
             const float N = fminf(h.w + 1.0f, Q.max_history);
             const float alpha = 1.0f / N;
             h = make_float4(h.x + alpha * (cs.x - h.x), h.y + alpha * (cs.y - h.y), h.z + alpha * (cs.z - h.z), N);
@@ -4573,7 +4600,7 @@ __global__ __launch_bounds__(64, 4) void adaptive_samples_kernel(const AdaptiveP
         if (Q.moments) Q.moments[pixel] = mo;
         if (Q.accum) {
             const float4 a = Q.accum[pixel];
-            const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
+            const f3 s = sums.sum();
             Q.accum[pixel] = make_float4(a.x + s.x, a.y + s.y, a.z + s.z, a.w + (float)paths);
         }
         c.mode = MODE_NEED;
@@ -4586,7 +4613,7 @@ __global__ __launch_bounds__(64, 4) void adaptive_samples_kernel(const AdaptiveP
             return;
         }
         rng.pix = pixel;
-        q0 = q1 = q2 = 0u;
+        sums = SampleSums{0u, 0u, 0u};
         sample = 0u;
         if (Q.history) h = Q.history[pixel];
         if (Q.moments) mo = Q.moments[pixel];
@@ -4594,57 +4621,26 @@ __global__ __launch_bounds__(64, 4) void adaptive_samples_kernel(const AdaptiveP
             begin_path();
         } else {  // exceeded recursion at once (Kernel.cu:79): every sample is 0, nothing is traced
             npaths += paths;
-            for (uint32_t j = 0; j < paths; j++) merge(0u, 0u, 0u);
+            for (uint32_t j = 0; j < paths; j++) merge(mk(0.0f, 0.0f, 0.0f));
             c.mode = MODE_ENDED;
         }
     };
-    if (lane < count) start(base + lane);
-    uint32_t taken = 64u;  // wave-uniform: entries of the wave's range handed out so far
-    while (__ballot(c.mode != MODE_DONE) != 0) {
-        if (c.mode == MODE_TRAV) {
-            uint32_t thr = P->regen_threshold;
-            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
-            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c, cnt, 64u,
-                                                                P->leaf_break);
-        }
-        if (c.mode == MODE_SHADE) {
-            if (COUNT_TESTS) cnt.wshade += wave_leader();
-            KParamsC* const q = kparams_reload();
-            f3 contrib;
-            const int res = shade<true, false, false>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att, rng, rtl,
-                                                      contrib);
-            bool ended = res == SHADE_ENDED;
-            if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
-                ended = true;
-                contrib = mk(0.0f, 0.0f, 0.0f);
-            }
-            if (!ended) {
-                v3_start_trace<WIDE>(q->num_nodes, c, nrays);
-            } else {
-                merge(quant12(contrib.x), quant12(contrib.y), quant12(contrib.z));
-                if (++sample < paths) begin_path();
-                else c.mode = MODE_ENDED;
-            }
+    const auto step = [&]() {
+        f3 contrib;
+        if (c.mode == MODE_SHADE && path_vertex<COUNT_TESTS>(w, att, rng, rtl, depth, contrib)) {
+            merge(contrib);
+            if (++sample < paths) begin_path();
+            else c.mode = MODE_ENDED;
         }
         if (c.mode == MODE_ENDED) store();
-        const uint64_t needm = __ballot(c.mode == MODE_NEED);
-        if (needm != 0) {
-            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
-            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088 beyond the skipped entries' turns)
-            if (c.mode == MODE_NEED) {
-                if (k < count) start(base + k);
-                else c.mode = MODE_DONE;
-            }
-        }
-    }
-    cnt.rays = nrays;
-    cnt.primary = npaths;
-    flush_counts<COUNT_TESTS>(*P, cnt);
+    };
+    ray_wave_run<COUNT_TESTS>(P, w, base, min(entries - base, Q.per_wave), start, step);
+    w.template finish<COUNT_TESTS>(*P, npaths);
 }
 
 // ---------------------------------------------------------------------------------------------------
 // A past frame's samples traced again in the scene as it is now, and compared with what that frame stored
-// (rt_temporal_gradient): adaptive_samples_kernel's schedule with strata as work items.  Stratum i = sy·sw + sx owns one
+// (rt_temporal_gradient): ray_wave_run and path_vertex with strata as work items.  Stratum i = sy·sw + sx owns one
 // pixel of its stride × stride block, (min(sx·stride + off_x, W − 1), min(sy·stride + off_y, H − 1)); a lane owns the
 // stratum from the first camera ray of sample 0 to its store.  Path j is the pixel's sample j of the Philox stream
 // (key, pixel, frame): camera_ray from block 0 of the sample's window, the bounce loop from block 1, rays from the root,
@@ -4666,22 +4662,14 @@ static_assert(offsetof(GradientParams, K) == 0, "philox_block and kparams_reload
 
 template <bool COUNT_TESTS, bool WIDE>
 __global__ __launch_bounds__(64, 4) void temporal_gradient_kernel(const GradientParams Q) {
-    using Entry = typename RefW<WIDE>::Entry;
     const KParams* P = &Q.K;
-    extern __shared__ float4 lds[];
-    const uint32_t lane = threadIdx.x & 63u;
-    Entry* const stk = reinterpret_cast<Entry*>(lds) + lane;
-    const __amdgpu_buffer_rsrc_t nrsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)P->nodes48, (short)0, (int)(P->num_nodes * 48u), 0x00020000);
-    stk[0] = (Entry)RefW<WIDE>::kSentinel;
-    stk[64] = (Entry)RefW<WIDE>::kSentinel;
-    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers n: base < n)
-    const uint32_t count = min(Q.n - base, Q.per_wave);  // strata of this wave's range
-    Counts cnt{0, 0, 0, 0, 0, 0, 0};
-    Cursor c{(int)RefW<WIDE>::kSentinel, 0, -1, 0u, 0u, FLT_MAX, MODE_DONE};
-    uint32_t nrays = 0u, npaths = 0u;
-    f3 ro = mk(0.0f, 0.0f, 0.0f), rd = ro, att = ro;
-    uint32_t q0 = 0u, q1 = 0u, q2 = 0u;  // the stratum's sample sums, 2^-12 units
+    RayWave<WIDE> w;
+    w.begin(P);
+    Cursor& c = w.c;
+    const uint32_t base = blockIdx.x * Q.per_wave;
+    uint32_t npaths = 0u;
+    f3 att = mk(0.0f, 0.0f, 0.0f);
+    SampleSums sums{0u, 0u, 0u};  // the stratum's
     uint32_t item = 0u, pixel = 0u, sample = 0u, depth = 0u;
     RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
     const bool rtl = P->rius_rtl != 0;
@@ -4689,16 +4677,14 @@ __global__ __launch_bounds__(64, 4) void temporal_gradient_kernel(const Gradient
     const auto begin_path = [&]() {
         KParamsC* const q = kparams_reload();
         const uint32_t g = pixel / q->width, x = pixel - g * q->width;
-        camera_ray(q, lane_camera(q, x, g), rng, ro, rd, sample);
+        camera_ray(q, lane_camera(q, x, g), rng, w.ro, w.rd, sample);
         att = mk(1.0f, 1.0f, 1.0f);
         depth = 0u;
         npaths++;
-        v3_start_trace<WIDE>(q->num_nodes, c, nrays);
+        v3_start_trace<WIDE>(q->num_nodes, c, w.nrays);
     };
     const auto store = [&]() {
-        const f3 s = mk((float)q0 * (1.0f / 4096.0f), (float)q1 * (1.0f / 4096.0f), (float)q2 * (1.0f / 4096.0f));  // pixel_sum
-        const float ns = (float)Q.samples;
-        const f3 cn = divs_rn(s, ns, recip_in_range(ns));  // rt_radiance_rays' mean
+        const f3 cn = sums.mean((float)Q.samples);  // rt_radiance_rays' mean
         const float4 co = Q.prev_color[pixel];             // (pixel < W·H: both coordinates are clamped)
         const float delta = (fabsf(cn.x - co.x) + fabsf(cn.y - co.y)) + fabsf(cn.z - co.z);
         const float level = ((cn.x > co.x ? cn.x : co.x) + (cn.y > co.y ? cn.y : co.y)) + (cn.z > co.z ? cn.z : co.z);
@@ -4712,7 +4698,7 @@ __global__ __launch_bounds__(64, 4) void temporal_gradient_kernel(const Gradient
         const uint32_t sy = i / Q.sw, sx = i - sy * Q.sw;
         pixel = min(sy * Q.stride + Q.off_y, P->height - 1u) * P->width + min(sx * Q.stride + Q.off_x, P->width - 1u);
         rng.pix = pixel;
-        q0 = q1 = q2 = 0u;
+        sums = SampleSums{0u, 0u, 0u};
         sample = 0u;
         if (P->max_depth != 0u) {
             begin_path();
@@ -4721,50 +4707,17 @@ __global__ __launch_bounds__(64, 4) void temporal_gradient_kernel(const Gradient
             c.mode = MODE_ENDED;
         }
     };
-    if (lane < count) start(base + lane);
-    uint32_t taken = 64u;  // wave-uniform: strata of the wave's range handed out so far
-    while (__ballot(c.mode != MODE_DONE) != 0) {
-        if (c.mode == MODE_TRAV) {
-            uint32_t thr = P->regen_threshold;
-            if (P->regen_live_frac) thr = min(thr, ((uint32_t)__popcll(__ballot(c.mode != MODE_DONE)) * P->regen_live_frac) >> 6);
-            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(nrsrc, P->nodes48, P->refs, P->prims, stk, thr, ro, rd, c, cnt, 64u,
-                                                                P->leaf_break);
-        }
-        if (c.mode == MODE_SHADE) {
-            if (COUNT_TESTS) cnt.wshade += wave_leader();
-            KParamsC* const q = kparams_reload();
-            f3 contrib;
-            const int res = shade<true, false, false>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, ro, rd, att, rng, rtl,
-                                                      contrib);
-            bool ended = res == SHADE_ENDED;
-            if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
-                ended = true;
-                contrib = mk(0.0f, 0.0f, 0.0f);
-            }
-            if (!ended) {
-                v3_start_trace<WIDE>(q->num_nodes, c, nrays);
-            } else {
-                q0 = sat_add(q0, quant12(contrib.x));
-                q1 = sat_add(q1, quant12(contrib.y));
-                q2 = sat_add(q2, quant12(contrib.z));
-                if (++sample < Q.samples) begin_path();
-                else c.mode = MODE_ENDED;
-            }
+    const auto step = [&]() {
+        f3 contrib;
+        if (c.mode == MODE_SHADE && path_vertex<COUNT_TESTS>(w, att, rng, rtl, depth, contrib)) {
+            sums.add(contrib);
+            if (++sample < Q.samples) begin_path();
+            else c.mode = MODE_ENDED;
         }
         if (c.mode == MODE_ENDED) store();
-        const uint64_t needm = __ballot(c.mode == MODE_NEED);
-        if (needm != 0) {
-            const uint32_t k = taken + __builtin_amdgcn_mbcnt_hi((uint32_t)(needm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)needm, 0u));
-            taken += (uint32_t)__popcll(needm);  // (at most per_wave + 64 <= 1088)
-            if (c.mode == MODE_NEED) {
-                if (k < count) start(base + k);
-                else c.mode = MODE_DONE;
-            }
-        }
-    }
-    cnt.rays = nrays;
-    cnt.primary = npaths;
-    flush_counts<COUNT_TESTS>(*P, cnt);
+    };
+    ray_wave_run<COUNT_TESTS>(P, w, base, wave_items(Q.n, base, Q.per_wave), start, step);
+    w.template finish<COUNT_TESTS>(*P, npaths);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -5415,6 +5368,83 @@ void fill_flat_tables(dev::KParams& P, const DeviceScene& S) {
     P.flat_runs[1] = S.flat_runs[1];
 }
 
+// ----- ... and the per-ray entry points (rt_trace_rays, rt_query_rays, rt_occluded_rays, rt_radiance_rays,
+// rt_adaptive_samples, rt_temporal_gradient: dev::RayWave's kernels) ----------------------------------------
+
+// LDS bytes of a wave's traversal stacks (dev::RayWave::begin); a BVH too deep for them fails in `who`'s name.
+int stack_lds(const char* who, const DeviceScene& S, size_t* lds) {
+    *lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
+    if (S.depth <= (uint32_t)dev::kStackMax && *lds <= kLdsLimit) return RT_OK;
+    set_error(std::string(who) + ": BVH too deep");
+    return RT_ERR_UNSUPPORTED;
+}
+
+// The traversal's tuning (rt_set_tuning), as dev::ray_wave_run reads it
+void fill_tuning(dev::KParams& P) {
+    P.regen_threshold = (uint32_t)g_regen_threshold;
+    P.regen_live_frac = (uint32_t)g_regen_live_frac;
+    P.leaf_break = (uint32_t)g_leaf_break;
+}
+
+// A path's depth limit, Random()'s fill order and the Philox stream's key and frame
+void fill_path(dev::KParams& P, const uint32_t max_depth, const uint32_t flags, const uint64_t seed, const uint32_t frame) {
+    P.max_depth = max_depth;
+    P.rius_rtl = (flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
+    P.rng_key_lo = (uint32_t)seed;
+    P.rng_key_hi = (uint32_t)(seed >> 32);
+    P.rng_frame = frame;
+}
+
+// Global pixel indices: one band of the whole frame, so that every field has a defined value
+void fill_whole_frame(dev::KParams& P, const uint32_t width, const uint32_t height) {
+    P.width = width;
+    P.height = height;
+    P.band_rows = 1u;
+    P.num_ranks = 1u;
+}
+
+// The automatic rays per lane: enough waves to fill the device (8 per SIMD), at most 16 rays per lane
+uint32_t auto_rays_per_lane(const uint32_t n) {
+    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, (uint64_t)n / (64ull * 8192ull)));
+}
+
+// A wave's share of `items` (rays_per_lane 0: the automatic setting) and the grid of single-wave workgroups that covers them
+uint32_t wave_grid(const uint32_t rays_per_lane, const uint32_t items, uint32_t* per_wave) {
+    *per_wave = 64u * (rays_per_lane ? rays_per_lane : auto_rays_per_lane(items));
+    return (uint32_t)(((uint64_t)items + *per_wave - 1) / *per_wave);
+}
+
+// The build of a per-ray kernel template <COUNT_TESTS, WIDE> for a call
+#define RT_RAY_KERNEL(name, count, wide)                                               \
+    ((wide) ? ((count) ? dev::name<true, true> : dev::name<false, true>) \
+            : ((count) ? dev::name<true, false> : dev::name<false, false>))
+
+template <class... Params, class... Args>
+int launch_rays(const char* who, void (*kernel)(Params...), const uint32_t grid, const size_t lds, const rt_stream stream,
+                const Args&... args) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, (hipStream_t)stream, args...);
+    return hip_check(hipGetLastError(), (std::string(who) + ": kernel launch").c_str(), RT_ERR_LAUNCH);
+}
+
+// The first two of a call's buffers that overlap, as its message; empty when none do.  spans[0 .. inputs) are read,
+// the rest written: an output is tested against every input, then against the outputs before it.  inputs == 0: every
+// pair is tested and named.
+struct Span {
+    const char* name;
+    const void* p;
+    uint64_t bytes;
+};
+std::string overlap_message(const Span* s, const int n, const int inputs) {
+    for (int i = inputs; i < n; i++)
+        for (int j = 0; j < i; j++)
+            if (overlaps(s[i].p, s[i].bytes, s[j].p, s[j].bytes)) {
+                if (inputs == 0) return std::string(s[i].name) + " overlaps " + s[j].name;
+                return j < inputs ? std::string("an output overlaps ") + s[j].name : std::string("outputs overlap each other");
+            }
+    return std::string();
+}
+
 int tile_kernel_of(const bool flat) { return flat ? kVarFlat : kVarV3Compact; }
 int persistent_kernel_of(const bool flat) { return flat ? kVarFlatPersistent : kVarV4; }
 
@@ -5611,34 +5641,22 @@ int rt_tile_entries_device(const rt_scene* scene, const rt_input_struct* inputs,
     return hip_check(hipGetLastError(), "rt_tile_entries_device: kernel launch", RT_ERR_LAUNCH);
 }
 
-// rt_trace_rays' automatic rays per lane: enough waves to fill the device (8 per SIMD), at most 16 rays per lane
-static uint32_t auto_rays_per_lane(const uint32_t n) {
-    return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(16, (uint64_t)n / (64ull * 8192ull)));
-}
-
 int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t* hits, uint64_t* counters,
                   int count_tests, rt_stream stream) {
     if (!scene || (n && (!rays || !hits))) { set_error("rt_trace_rays: NULL argument"); return RT_ERR_INVALID_ARGUMENT; }
     if (n == 0) return RT_OK;
     const DeviceScene& S = scene->dev;
-    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
-    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_trace_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    size_t lds;
+    if (const int rc = stack_lds("rt_trace_rays", S, &lds)) return rc;
     dev::KParams P;
     std::memset(&P, 0, sizeof(P));
     fill_scene_tables(P, S);
     P.counters = (unsigned long long*)counters;
-    P.regen_threshold = (uint32_t)g_regen_threshold;
-    P.regen_live_frac = (uint32_t)g_regen_live_frac;
-    P.leaf_break = (uint32_t)g_leaf_break;
-    const uint32_t per_wave = 64u * auto_rays_per_lane(n);
-    const uint32_t grid = (uint32_t)(((uint64_t)n + per_wave - 1) / per_wave);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    const bool count = count_tests && counters;
-    const auto kernel = S.wide_refs ? (count ? dev::trace_rays_kernel<true, true> : dev::trace_rays_kernel<false, true>)
-                                    : (count ? dev::trace_rays_kernel<true, false> : dev::trace_rays_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, P, (const float4*)rays, n, per_wave, (int2*)hits);
-    return hip_check(hipGetLastError(), "rt_trace_rays: kernel launch", RT_ERR_LAUNCH);
+    fill_tuning(P);
+    uint32_t per_wave;
+    const uint32_t grid = wave_grid(0u, n, &per_wave);
+    return launch_rays("rt_trace_rays", RT_RAY_KERNEL(trace_rays_kernel, count_tests && counters, S.wide_refs), grid, lds, stream,
+                       P, (const float4*)rays, n, per_wave, (int2*)hits);
 }
 
 int rt_gbuffer(const rt_scene* scene, const rt_gbuffer_args* a, rt_stream stream) {
@@ -5693,29 +5711,25 @@ int rt_query_rays(const rt_scene* scene, const rt_query_args* a, rt_stream strea
     if (a->flags != 0 || a->reserved != 0) return bad("flags and reserved must be 0");
     if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
     const uint64_t n = a->n;
-    const void* const outs[6] = {a->normal_depth, a->albedo, a->prim_id, a->uv, a->material, a->hits};
-    const uint64_t out_bytes[6] = {n * 16u, n * 16u, n * 4u, n * 8u, n * 4u, n * 8u};
+    const Span spans[7] = {{"rays", a->rays, n * 32u},      {"", a->normal_depth, n * 16u}, {"", a->albedo, n * 16u},
+                           {"", a->prim_id, n * 4u},        {"", a->uv, n * 8u},            {"", a->material, n * 4u},
+                           {"", a->hits, n * 8u}};
     bool any = false;
-    for (int o = 0; o < 6; o++) any = any || outs[o] != nullptr;
+    for (int o = 1; o < 7; o++) any = any || spans[o].p != nullptr;
     if (!any) return bad("no output buffer");
     if (n == 0) return RT_OK;  // nothing to trace
     if (!a->rays) return bad("NULL rays");
-    for (int o = 0; o < 6; o++) {
-        if (overlaps(outs[o], out_bytes[o], a->rays, n * 32u)) return bad("an output overlaps rays");
-        for (int p = 0; p < o; p++)
-            if (overlaps(outs[o], out_bytes[o], outs[p], out_bytes[p])) return bad("outputs overlap each other");
-    }
+    const std::string clash = overlap_message(spans, 7, 1);
+    if (!clash.empty()) return bad(clash.c_str());
     if (!scene) return bad("NULL scene");
     const DeviceScene& S = scene->dev;
-    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
-    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_query_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    size_t lds;
+    if (const int rc = stack_lds("rt_query_rays", S, &lds)) return rc;
     dev::QueryParams Q;
     std::memset(&Q, 0, sizeof(Q));
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
-    P.regen_threshold = (uint32_t)g_regen_threshold;
-    P.regen_live_frac = (uint32_t)g_regen_live_frac;
-    P.leaf_break = (uint32_t)g_leaf_break;
+    fill_tuning(P);
     Q.rays = (const float4*)a->rays;
     Q.normal_depth = (float4*)a->normal_depth;
     Q.albedo = (float4*)a->albedo;
@@ -5725,15 +5739,10 @@ int rt_query_rays(const rt_scene* scene, const rt_query_args* a, rt_stream strea
     Q.hits = (int2*)a->hits;
     Q.source = (const int32_t*)S.prim_source;
     Q.n = a->n;
-    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->n));
-    const uint32_t grid = (uint32_t)((n + Q.per_wave - 1) / Q.per_wave);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    if (S.wide_refs)
-        hipLaunchKernelGGL(dev::query_rays_kernel<true>, dim3(grid), dim3(64), lds, s, Q);
-    else
-        hipLaunchKernelGGL(dev::query_rays_kernel<false>, dim3(grid), dim3(64), lds, s, Q);
-    return hip_check(hipGetLastError(), "rt_query_rays: kernel launch", RT_ERR_LAUNCH);
+    const uint32_t grid = wave_grid(a->rays_per_lane, a->n, &Q.per_wave);
+    // (no counting build)
+    return launch_rays("rt_query_rays", S.wide_refs ? dev::query_rays_kernel<true> : dev::query_rays_kernel<false>, grid, lds,
+                       stream, Q);
 }
 
 int rt_occluded_rays(const rt_scene* scene, const rt_occlusion_args* a, rt_stream stream) {
@@ -5751,38 +5760,29 @@ int rt_occluded_rays(const rt_scene* scene, const rt_occlusion_args* a, rt_strea
     const uint64_t n = a->n;
     if (n == 0) return RT_OK;  // nothing to trace
     if (!a->rays) return bad("NULL rays");
-    const void* const outs[3] = {a->occluded, a->blocker, a->counters};
-    const uint64_t out_bytes[3] = {n, n * 4u, (uint64_t)RT_COUNTERS_WORDS * 8u};
-    for (int o = 0; o < 3; o++) {
-        if (overlaps(outs[o], out_bytes[o], a->rays, n * 32u)) return bad("an output overlaps rays");
-        for (int p = 0; p < o; p++)
-            if (overlaps(outs[o], out_bytes[o], outs[p], out_bytes[p])) return bad("outputs overlap each other");
-    }
+    const Span spans[4] = {{"rays", a->rays, n * 32u},
+                           {"", a->occluded, n},
+                           {"", a->blocker, n * 4u},
+                           {"", a->counters, (uint64_t)RT_COUNTERS_WORDS * 8u}};
+    const std::string clash = overlap_message(spans, 4, 1);
+    if (!clash.empty()) return bad(clash.c_str());
     if (!scene) return bad("NULL scene");
     const DeviceScene& S = scene->dev;
-    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
-    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_occluded_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    size_t lds;
+    if (const int rc = stack_lds("rt_occluded_rays", S, &lds)) return rc;
     dev::OcclusionParams Q;
     std::memset(&Q, 0, sizeof(Q));
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
     P.counters = (unsigned long long*)a->counters;
-    P.regen_threshold = (uint32_t)g_regen_threshold;
-    P.regen_live_frac = (uint32_t)g_regen_live_frac;
-    P.leaf_break = (uint32_t)g_leaf_break;
+    fill_tuning(P);
     Q.rays = (const float4*)a->rays;
     Q.occluded = a->occluded;
     Q.blocker = a->blocker;
     Q.source = (const int32_t*)S.prim_source;
     Q.n = a->n;
-    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->n));
-    const uint32_t grid = (uint32_t)((n + Q.per_wave - 1) / Q.per_wave);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    const auto kernel = S.wide_refs ? (a->count_tests ? dev::occlusion_rays_kernel<true, true> : dev::occlusion_rays_kernel<false, true>)
-                                    : (a->count_tests ? dev::occlusion_rays_kernel<true, false> : dev::occlusion_rays_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
-    return hip_check(hipGetLastError(), "rt_occluded_rays: kernel launch", RT_ERR_LAUNCH);
+    const uint32_t grid = wave_grid(a->rays_per_lane, a->n, &Q.per_wave);
+    return launch_rays("rt_occluded_rays", RT_RAY_KERNEL(occlusion_rays_kernel, a->count_tests, S.wide_refs), grid, lds, stream, Q);
 }
 
 int rt_camera_rays(const rt_camera_rays_args* a, rt_stream stream) {
@@ -5810,11 +5810,8 @@ int rt_camera_rays(const rt_camera_rays_args* a, rt_stream stream) {
     dev::CameraRaysParams Q;
     std::memset(&Q, 0, sizeof(Q));
     dev::KParams& P = Q.K;
-    if (a->pixels) {  // (global indices: one band of the whole frame, so that every field has a defined value)
-        P.width = a->width;
-        P.height = a->height;
-        P.band_rows = 1u;
-        P.num_ranks = 1u;
+    if (a->pixels) {  // (global indices)
+        fill_whole_frame(P, a->width, a->height);
     } else {
         fill_frame(P, a->width, a->height, a->tiling, false);
     }
@@ -5859,32 +5856,25 @@ int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* a, rt_stream
     const uint64_t n = a->n;
     if (n == 0) return RT_OK;  // nothing to trace
     if (!a->rays) return bad("NULL rays");
-    const void* const outs[3] = {a->sum, a->mean, a->counters};
-    const uint64_t out_bytes[3] = {n * 16u, n * 16u, (uint64_t)RT_COUNTERS_WORDS * 8u};
-    for (int o = 0; o < 3; o++) {
-        if (overlaps(outs[o], out_bytes[o], a->rays, n * 32u)) return bad("an output overlaps rays");
-        if (overlaps(outs[o], out_bytes[o], a->stream_ids, n * 4u)) return bad("an output overlaps stream_ids");
-        for (int p = 0; p < o; p++)
-            if (overlaps(outs[o], out_bytes[o], outs[p], out_bytes[p])) return bad("outputs overlap each other");
-    }
+    const Span spans[5] = {{"rays", a->rays, n * 32u},
+                           {"stream_ids", a->stream_ids, n * 4u},
+                           {"", a->sum, n * 16u},
+                           {"", a->mean, n * 16u},
+                           {"", a->counters, (uint64_t)RT_COUNTERS_WORDS * 8u}};
+    const std::string clash = overlap_message(spans, 5, 2);
+    if (!clash.empty()) return bad(clash.c_str());
     if (!scene) return bad("NULL scene");
     const DeviceScene& S = scene->dev;
-    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
-    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_radiance_rays: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    size_t lds;
+    if (const int rc = stack_lds("rt_radiance_rays", S, &lds)) return rc;
     dev::RadianceDirectParams DQ;
     std::memset(&DQ, 0, sizeof(DQ));
     dev::RadianceParams& Q = DQ.R;
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
     P.counters = (unsigned long long*)a->counters;
-    P.regen_threshold = (uint32_t)g_regen_threshold;
-    P.regen_live_frac = (uint32_t)g_regen_live_frac;
-    P.leaf_break = (uint32_t)g_leaf_break;
-    P.max_depth = a->max_depth;
-    P.rius_rtl = (a->flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
-    P.rng_key_lo = (uint32_t)a->rng_seed;
-    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
-    P.rng_frame = a->rng_frame;
+    fill_tuning(P);
+    fill_path(P, a->max_depth, a->flags, a->rng_seed, a->rng_frame);
     for (int i = 0; i < 3; i++) {
         P.bg0[i] = a->background_start[i];
         P.bg1[i] = a->background_end[i];
@@ -5894,26 +5884,18 @@ int rt_radiance_rays(const rt_scene* scene, const rt_radiance_args* a, rt_stream
     Q.sum = (float4*)a->sum;
     Q.mean = (float4*)a->mean;
     Q.n = a->n;
-    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->n));
     Q.samples = a->samples_per_ray;
     Q.sample_base = a->sample_base;
     Q.stream_base = a->stream_base;
-    const uint32_t grid = (uint32_t)((n + Q.per_wave - 1) / Q.per_wave);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
+    const uint32_t grid = wave_grid(a->rays_per_lane, a->n, &Q.per_wave);
     if (direct && S.num_lights != 0u) {  // (without a sampled light the flagged call is the flagless one)
         DQ.lights = (const float4*)S.light_table;
         DQ.light_flags = (const uint32_t*)S.light_table + (size_t)S.num_rects * 8u;
         DQ.num_lights = S.num_lights;
-        const auto dkernel = S.wide_refs ? (a->count_tests ? dev::radiance_direct_kernel<true, true> : dev::radiance_direct_kernel<false, true>)
-                                         : (a->count_tests ? dev::radiance_direct_kernel<true, false> : dev::radiance_direct_kernel<false, false>);
-        hipLaunchKernelGGL(dkernel, dim3(grid), dim3(64), lds, s, DQ);
-        return hip_check(hipGetLastError(), "rt_radiance_rays: kernel launch", RT_ERR_LAUNCH);
+        return launch_rays("rt_radiance_rays", RT_RAY_KERNEL(radiance_direct_kernel, a->count_tests, S.wide_refs), grid, lds, stream,
+                           DQ);
     }
-    const auto kernel = S.wide_refs ? (a->count_tests ? dev::radiance_rays_kernel<true, true> : dev::radiance_rays_kernel<false, true>)
-                                    : (a->count_tests ? dev::radiance_rays_kernel<true, false> : dev::radiance_rays_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
-    return hip_check(hipGetLastError(), "rt_radiance_rays: kernel launch", RT_ERR_LAUNCH);
+    return launch_rays("rt_radiance_rays", RT_RAY_KERNEL(radiance_rays_kernel, a->count_tests, S.wide_refs), grid, lds, stream, Q);
 }
 
 int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a, rt_stream stream) {
@@ -5940,34 +5922,28 @@ int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a
     if (cap == 0) return RT_OK;  // nothing to trace
     if (!a->pixels) return bad("NULL pixels");
     if (n == 0) return bad("an empty frame (width or height 0) with capacity > 0");
-    const char* const names[7] = {"pixels", "samples", "count", "counters", "history", "moments", "accum"};
-    const void* const bufs[7] = {a->pixels, a->samples, a->count, a->counters, a->history, a->moments, a->accum};
-    const uint64_t bytes[7] = {cap * 4u, cap * 4u, 4u, (uint64_t)RT_COUNTERS_WORDS * 8u, n * 16u, n * 8u, n * 16u};
-    for (int i = 0; i < 7; i++)
-        for (int j = 0; j < i; j++)
-            if (overlaps(bufs[i], bytes[i], bufs[j], bytes[j])) return bad(std::string(names[i]) + " overlaps " + names[j]);
+    const Span spans[7] = {{"pixels", a->pixels, cap * 4u},
+                           {"samples", a->samples, cap * 4u},
+                           {"count", a->count, 4u},
+                           {"counters", a->counters, (uint64_t)RT_COUNTERS_WORDS * 8u},
+                           {"history", a->history, n * 16u},
+                           {"moments", a->moments, n * 8u},
+                           {"accum", a->accum, n * 16u}};
+    const std::string clash = overlap_message(spans, 7, 0);
+    if (!clash.empty()) return bad(clash);
     if (!scene) return bad("NULL scene");
     const DeviceScene& S = scene->dev;
-    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
-    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_adaptive_samples: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    size_t lds;
+    if (const int rc = stack_lds("rt_adaptive_samples", S, &lds)) return rc;
     dev::AdaptiveParams Q;
     std::memset(&Q, 0, sizeof(Q));
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
-    P.width = a->width;  // (global indices: one band of the whole frame, as rt_camera_rays' sparse form)
-    P.height = a->height;
-    P.band_rows = 1u;
-    P.num_ranks = 1u;
+    fill_whole_frame(P, a->width, a->height);  // (global indices, as rt_camera_rays' sparse form)
     fill_camera(P, a->inputs, a->width, a->height);  // (the sky too)
     P.counters = (unsigned long long*)a->counters;
-    P.regen_threshold = (uint32_t)g_regen_threshold;
-    P.regen_live_frac = (uint32_t)g_regen_live_frac;
-    P.leaf_break = (uint32_t)g_leaf_break;
-    P.max_depth = a->max_depth;
-    P.rius_rtl = (a->flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
-    P.rng_key_lo = (uint32_t)a->rng_seed;
-    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
-    P.rng_frame = a->rng_frame;
+    fill_tuning(P);
+    fill_path(P, a->max_depth, a->flags, a->rng_seed, a->rng_frame);
     Q.pixels = a->pixels;
     Q.samples = a->samples;
     Q.count = a->count;
@@ -5975,18 +5951,13 @@ int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a
     Q.moments = (float2*)a->moments;
     Q.accum = (float4*)a->accum;
     Q.capacity = a->capacity;
-    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(a->capacity));
     Q.spp = a->samples_per_pixel;
     Q.max_samples = a->max_samples;
     Q.sample_base = a->sample_base;
     Q.max_history = (float)a->max_history;
-    const uint32_t grid = (uint32_t)((cap + Q.per_wave - 1) / Q.per_wave);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    const auto kernel = S.wide_refs ? (a->count_tests ? dev::adaptive_samples_kernel<true, true> : dev::adaptive_samples_kernel<false, true>)
-                                    : (a->count_tests ? dev::adaptive_samples_kernel<true, false> : dev::adaptive_samples_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
-    return hip_check(hipGetLastError(), "rt_adaptive_samples: kernel launch", RT_ERR_LAUNCH);
+    const uint32_t grid = wave_grid(a->rays_per_lane, a->capacity, &Q.per_wave);
+    return launch_rays("rt_adaptive_samples", RT_RAY_KERNEL(adaptive_samples_kernel, a->count_tests, S.wide_refs), grid, lds,
+                       stream, Q);
 }
 
 int rt_temporal_gradient(const rt_scene* scene, const rt_temporal_gradient_args* a, rt_stream stream) {
@@ -6014,53 +5985,41 @@ int rt_temporal_gradient(const rt_scene* scene, const rt_temporal_gradient_args*
     const uint64_t strata = (uint64_t)sw * sh;
     if (!a->prev_color) return bad("NULL prev_color");
     if (!a->gradient) return bad("NULL gradient");
-    const char* const names[5] = {"prev_color", "gradient", "resample", "pixel", "counters"};
-    const void* const bufs[5] = {a->prev_color, a->gradient, a->resample, a->pixel, a->counters};
-    const uint64_t bytes[5] = {n * 16u, strata * 8u, strata * 16u, strata * 4u, (uint64_t)RT_COUNTERS_WORDS * 8u};
-    for (int i = 0; i < 5; i++)
-        for (int j = 0; j < i; j++)
-            if (overlaps(bufs[i], bytes[i], bufs[j], bytes[j])) return bad(std::string(names[i]) + " overlaps " + names[j]);
+    const Span spans[5] = {{"prev_color", a->prev_color, n * 16u},
+                           {"gradient", a->gradient, strata * 8u},
+                           {"resample", a->resample, strata * 16u},
+                           {"pixel", a->pixel, strata * 4u},
+                           {"counters", a->counters, (uint64_t)RT_COUNTERS_WORDS * 8u}};
+    const std::string clash = overlap_message(spans, 5, 0);
+    if (!clash.empty()) return bad(clash);
     if (!scene) return bad("NULL scene");
     const DeviceScene& S = scene->dev;
-    const size_t lds = (size_t)(S.depth + 2) * 64 * (S.wide_refs ? 4 : 2);
-    if (S.depth > (uint32_t)dev::kStackMax || lds > kLdsLimit) { set_error("rt_temporal_gradient: BVH too deep"); return RT_ERR_UNSUPPORTED; }
+    size_t lds;
+    if (const int rc = stack_lds("rt_temporal_gradient", S, &lds)) return rc;
     dev::GradientParams Q;
     std::memset(&Q, 0, sizeof(Q));
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
-    P.width = a->width;  // (global indices: one band of the whole frame, as rt_adaptive_samples)
-    P.height = a->height;
-    P.band_rows = 1u;
-    P.num_ranks = 1u;
+    fill_whole_frame(P, a->width, a->height);  // (global indices, as rt_adaptive_samples)
     fill_camera(P, a->inputs, a->width, a->height);  // (the sky too)
     P.counters = (unsigned long long*)a->counters;
-    P.regen_threshold = (uint32_t)g_regen_threshold;
-    P.regen_live_frac = (uint32_t)g_regen_live_frac;
-    P.leaf_break = (uint32_t)g_leaf_break;
-    P.max_depth = a->max_depth;
-    P.rius_rtl = (a->flags & RT_FLAG_RIUS_LEFT_TO_RIGHT) ? 0u : 1u;
-    P.rng_key_lo = (uint32_t)a->rng_seed;
-    P.rng_key_hi = (uint32_t)(a->rng_seed >> 32);
-    P.rng_frame = a->rng_frame;
+    fill_tuning(P);
+    fill_path(P, a->max_depth, a->flags, a->rng_seed, a->rng_frame);
     Q.prev_color = (const float4*)a->prev_color;
     Q.gradient = (float2*)a->gradient;
     Q.resample = (float4*)a->resample;
     Q.pixel = a->pixel;
     Q.n = (uint32_t)strata;
-    Q.per_wave = 64u * (a->rays_per_lane ? a->rays_per_lane : auto_rays_per_lane(Q.n));
     Q.sw = sw;
     Q.stride = a->stride;
     Q.off_x = a->offset_x;
     Q.off_y = a->offset_y;
     Q.samples = a->samples_per_pixel;
-    const uint32_t grid = (uint32_t)((strata + Q.per_wave - 1) / Q.per_wave);
-    hipStream_t s = (hipStream_t)stream;
-    (void)hipGetLastError();
-    const auto kernel = S.wide_refs ? (a->count_tests ? dev::temporal_gradient_kernel<true, true> : dev::temporal_gradient_kernel<false, true>)
-                                    : (a->count_tests ? dev::temporal_gradient_kernel<true, false> : dev::temporal_gradient_kernel<false, false>);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, s, Q);
-    return hip_check(hipGetLastError(), "rt_temporal_gradient: kernel launch", RT_ERR_LAUNCH);
+    const uint32_t grid = wave_grid(a->rays_per_lane, Q.n, &Q.per_wave);
+    return launch_rays("rt_temporal_gradient", RT_RAY_KERNEL(temporal_gradient_kernel, a->count_tests, S.wide_refs), grid, lds,
+                       stream, Q);
 }
+#undef RT_RAY_KERNEL
 
 int rt_set_pixel_cost(void* buffer, uint64_t bytes) {
     g_pixel_cost = (bytes && buffer) ? (uint8_t*)buffer : nullptr;

@@ -8,20 +8,9 @@ counts the build gave, within the 128 of __launch_bounds__(64, 
 traversals' diagnostic counts and ask for two waves per SIMD; they too stay out of scratch.  The kernel is a template of
 its own, and shade()'s new template parameter is defaulted, so every kernel it stands beside — radiance_rays_kernel
 among them — keeps the VGPR count the other resource tests pin."""
-from test_adaptive_resources import SAMPLES_VGPRS as ADAPTIVE_VGPRS
-from test_occlusion_resources import PRODUCT_VGPRS as OCCLUSION_VGPRS
-from test_query_resources import NEW_VGPRS, UNCHANGED_VGPRS
-from test_radiance_resources import PRODUCT_VGPRS as RADIANCE_VGPRS
-from test_variance_resources import UNCHANGED_VGPRS as FILTER_VGPRS
+from test_ray_kernel_resources import DIRECT_VGPRS as PRODUCT_VGPRS  # (the figures: one table)
+from test_ray_kernel_resources import _direct
 from test_variance_resources import kernel_metadata
-
-
-def _direct(count, wide):
-    return f"_ZN2rt3dev22radiance_direct_kernelILb{count}ELb{wide}EEEvNS0_20RadianceDirectParamsE"
-
-
-# VGPRs the build gave the product kernels (4 waves per SIMD asked for: at most 128)
-PRODUCT_VGPRS = {_direct(0, 0): 101, _direct(0, 1): 103}
 
 
 def test_direct_light_kernels_use_no_scratch(tmp_path):
@@ -39,14 +28,3 @@ def test_direct_light_kernels_use_no_scratch(tmp_path):
         assert vgprs <= 128
     for wide in (0, 1):  # the counting builds: two waves per SIMD asked for
         assert meta[_direct(1, wide)]["vgpr_count"] <= 256
-
-
-def test_parent_kernels_keep_their_registers(tmp_path):
-    meta = kernel_metadata(tmp_path)
-    assert all(k in meta for k in PRODUCT_VGPRS)  # (beside the new kernels: the figures below are what they were without them)
-    pinned = {**NEW_VGPRS, **UNCHANGED_VGPRS, **OCCLUSION_VGPRS, **RADIANCE_VGPRS, **FILTER_VGPRS, **ADAPTIVE_VGPRS}
-    for k, vgprs in pinned.items():
-        assert k in meta, k
-        assert meta[k]["vgpr_count"] == vgprs, (k, meta[k])
-        assert meta[k]["private_segment_fixed_size"] == 0, (k, meta[k])
-        assert meta[k]["vgpr_spill_count"] == 0, (k, meta[k])

@@ -6,17 +6,10 @@ scratch (no private segment, no VGPR spills), no static LDS (the traversal stack
 depth), keep no more SGPRs in VGPR lanes than query_rays_kernel does, and have the VGPR counts the build gave
 (DESIGN.md §16).  The any-hit mode is a template parameter of v3_traverse whose default leaves every other
 instantiation as it was: query_rays_kernel, trace_rays_kernel<false, *> and gbuffer_kernel keep the VGPR counts
-tests/test_query_resources.py pins."""
-from test_query_resources import NEW_VGPRS, UNCHANGED_VGPRS, _query
+tests/test_ray_kernel_resources.py pins (one table and one test for every per-ray kernel)."""
+from test_ray_kernel_resources import OCCLUSION_VGPRS as PRODUCT_VGPRS  # (the figures: one table)
+from test_ray_kernel_resources import _occlusion, _query
 from test_variance_resources import kernel_metadata
-
-
-def _occlusion(count, wide):
-    return f"_ZN2rt3dev21occlusion_rays_kernelILb{count}ELb{wide}EEEvNS0_15OcclusionParamsE"
-
-
-# VGPRs the build gave the product kernels (4 waves per SIMD asked for, 8 fit; the WIDE build holds 32-bit entries)
-PRODUCT_VGPRS = {_occlusion(0, 0): 59, _occlusion(0, 1): 61}
 
 
 def test_occlusion_kernels_use_no_scratch(tmp_path):
@@ -36,13 +29,3 @@ def test_occlusion_kernels_use_no_scratch(tmp_path):
     for wide in (0, 1):
         assert meta[_occlusion(1, wide)]["private_segment_fixed_size"] == 0
         assert meta[_occlusion(1, wide)]["group_segment_fixed_size"] == 0
-
-
-def test_closest_hit_kernels_keep_their_registers(tmp_path):
-    meta = kernel_metadata(tmp_path)
-    assert all(k in meta for k in PRODUCT_VGPRS)  # (beside the new kernels: the figures below are what they were without them)
-    for k, vgprs in {**NEW_VGPRS, **UNCHANGED_VGPRS}.items():
-        assert k in meta, k
-        assert meta[k]["vgpr_count"] == vgprs, (k, meta[k])
-        assert meta[k]["private_segment_fixed_size"] == 0, (k, meta[k])
-        assert meta[k]["vgpr_spill_count"] == 0, (k, meta[k])

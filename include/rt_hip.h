@@ -388,7 +388,9 @@ int rt_set_ray_dump(void* rays, uint32_t capacity, uint32_t* count, uint32_t dep
  * (BVHNode::Hit semantics, Hittable.cuh:387-439; t in (0.001, FLT_MAX)): hits[2i] = the primitive's index in the
  * scene's BVH order or -1, hits[2i + 1] = the hit distance's bits.  counters: optional device uint64[RT_COUNTERS_WORDS]
  * ([0] rays; with count_tests also box and primitive tests and wave iterations, as rt_render).  Asynchronous on
- * `stream`.  Scenes of any size; a BVH deeper than 64 levels is refused (RT_ERR_UNSUPPORTED, "BVH too deep"). */
+ * `stream`.  Scenes of any size; a BVH deeper than 64 levels is refused (RT_ERR_UNSUPPORTED, "BVH too deep").
+ * Direction components may be +0 or -0, and d need not be normalised: see "Rays of the caller's own" under
+ * rt_occluded_rays for the one unspecified ray (in a rectangle's plane) and the range of |d| and t. */
 int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t* hits, uint64_t* counters,
                   int count_tests, rt_stream stream);
 
@@ -407,7 +409,11 @@ int rt_trace_rays(const rt_scene* scene, const float* rays, uint32_t n, int32_t*
  * asynchronous launch on `stream`; every element is written by one lane, without atomics, so two calls give the same
  * bits.  RT_ERR_INVALID_ARGUMENT, before any device call: NULL args, NULL rays with n > 0, no output buffer, an
  * output that overlaps `rays` or another output, rays_per_lane above 16, non-zero flags or reserved.  n = 0: RT_OK.
- * An empty scene gives all misses.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED ("BVH too deep"). */
+ * An empty scene gives all misses.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED ("BVH too deep").
+ * Rays with zero direction components, +0 or -0, are fully specified (a straight-down pick ray (0, -1, 0) gets the
+ * geometric closest hit like any other ray), with one exception: a ray lying in a rectangle's plane gets an unspecified
+ * value.  d is not normalised; the range of |d| and t with specified results, and the reason for the exception, are
+ * given under rt_occluded_rays ("Rays of the caller's own") and hold for this call and rt_trace_rays alike. */
 typedef struct rt_query_args {
     const float* rays;      /* device, n x 2 float4: (origin, -), (direction, -), as rt_trace_rays */
     float*   normal_depth;
@@ -435,6 +441,19 @@ int rt_query_rays(const rt_scene* scene, const rt_query_args* args, rt_stream st
  *   (Hittable.cuh:80-110); a rectangle for tmin <= t <= tmax inside its extent (Hittable.cuh:155-166).  tmax may be
  *   FLT_MAX or +inf, tmin may be 0 or negative.  Rays with a non-finite origin or direction component get an
  *   unspecified value (and touch no memory but the scene's tables and their own elements).
+ *   Rays of the caller's own (this call, rt_query_rays and rt_trace_rays).  Zero direction components, +0 or -0, are
+ *   otherwise fully specified; the sign of a zero changes no output bit.  The exception: a ray lying in a rectangle's
+ *   plane (d_k = 0 and o_k equal to the plane coordinate k of an active XY/XZ/YZ rectangle) gets an unspecified value,
+ *   because the reference's own test yields t = (k - o_k) * (1 / d_k) = 0 * inf = NaN there, which fails none of its
+ *   comparisons: it accepts the ray whatever the rectangle's extent, a definition no box-culling traversal can meet.
+ *   Magnitudes: results are specified for 2^-32 <= |d| <= 2^32 and hits at t <= 1e14 (in units of |d|), on scenes
+ *   within 1e4 units of the origin.  The traversal clamps 1 / d_k to +-1e20, so along an axis whose component is zero
+ *   (or below 1e-20 in magnitude) a node's slab becomes |t| <= delta * 1e20 with delta the origin's depth inside it;
+ *   a ray that hits a primitive starts, on such an axis, inside the primitive's extent and so at least the box
+ *   padding (1e-5 * |plane| + 1e-6, prim_box) inside every box that holds it: delta * 1e20 >= 1e14.  Beyond that t
+ *   (an axis-aligned ray with |d| near 2^-70, say) a box the ray passes through is culled.  Inside 2^+-32 the sphere
+ *   test's squares (d.d, b * b, a * c) stay normal floats, and scaling d by a power of two inside the range scales t
+ *   by its inverse and changes nothing else, bit for bit (the fixed tmin of 0.001 of the closest-hit calls aside).
  *   blocker[i]: the index in rt_scene_desc.hittables (rt_gbuffer's prim_id meaning) of the primitive that ended the
  *   ray's traversal — some primitive the ray hits within its range, not necessarily the nearest — or -1.
  * The range never shrinks during a traversal, so the primitive that ends it depends on the ray alone: both outputs are

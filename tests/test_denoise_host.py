@@ -175,11 +175,12 @@ def _candidates(scene, o: np.ndarray, d: np.ndarray) -> np.ndarray:
     return out
 
 
-def closest_hits(scene, o: np.ndarray, d: np.ndarray, records: bool = False):
+def closest_hits(scene, o: np.ndarray, d: np.ndarray, records: bool = False, prefilter_d: np.ndarray | None = None):
     """Brute-force closest hit of rays (N, 3): ids (N,) (index into scene.hittables or -1) and, with records, the
-    oracle's hit record of each."""
+    oracle's hit record of each.  prefilter_d: the directions the superset is built from, for rays whose |d| is far
+    from 1 (_candidates' absolute margins assume lengths near 1; a positive multiple of d spans the same half-line)."""
     L = po.lib()
-    cand = _candidates(scene, o, d)
+    cand = _candidates(scene, o, d if prefilter_d is None else prefilter_d)
     ids = np.full(o.shape[0], -1, dtype=np.int32)
     recs = [None] * o.shape[0] if records else None
     o, d = np.ascontiguousarray(o, dtype=F), np.ascontiguousarray(d, dtype=F)

@@ -20,6 +20,7 @@ from cudaraytracer_amd._lib import RTError, lib
 from cudaraytracer_amd.renderer import DeviceScene, Renderer
 from helpers import digest, image_stats, load_golden
 from oracle import py_oracle as po
+from ray_families import small_rects_scene as _small_rects_scene
 
 pytestmark = pytest.mark.gpu
 
@@ -684,25 +685,6 @@ def test_adaptive_tile_order_changes_schedule_not_pixels():
         np.testing.assert_array_equal(row_major, ref)
     finally:
         lib().rt_set_tuning(5, prev if prev >= 0 else 1)
-
-
-def _small_rects_scene():
-    """48 small axis-aligned rectangles (0.3-0.8 units) scattered around the origin, Lambertian."""
-    rng = np.random.default_rng(11)
-    n = 48
-    h = (abi.HittableDesc * n)()
-    m = (abi.MaterialDesc * n)()
-    for i in range(n):
-        h[i].type = (abi.RT_XYRECT, abi.RT_XZRECT, abi.RT_YZRECT)[i % 3]
-        h[i].is_active = 1
-        h[i].center[:] = [float(v) for v in rng.uniform(-6.0, 6.0, 3).astype(np.float32)]
-        h[i].width, h[i].height = (float(v) for v in rng.uniform(0.3, 0.8, 2).astype(np.float32))
-        h[i].material = i
-        m[i].type = abi.RT_LAMBERTIAN
-        m[i].albedo.type = abi.RT_CONSTANT
-        m[i].albedo.image = -1
-        m[i].albedo.color[:] = [float(v) for v in rng.uniform(0.2, 0.9, 3).astype(np.float32)]
-    return scenes.Scene(h, m, [])
 
 
 @pytest.mark.parametrize("rng", ["xorwow", "philox"])

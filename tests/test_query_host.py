@@ -7,7 +7,8 @@ through the oracle's primitive tests (closest_hits(..., records=True)), the reco
 gbuffer_reference derives it (a miss gets (0, 0, 0, 0): no camera, no sky), and — beyond rt_gbuffer's planes — the
 surface's (u, v) for every sphere and rectangle and the hittable's material index.  `uv64` is the same (u, v) in float64
 from the float64 hit point; the spread between the two is what the GPU test's uv bound is built from.  `decidable` is
-gbuffer_reference's rule: the centre ray and the four rays shifted by +-1/64 pixel hit the same primitive."""
+gbuffer_reference's rule: the centre ray and the four rays shifted by +-1/64 pixel hit the same primitive.
+records_reference is the same derivation for any rays and any set of nearby rays (tests/ray_families.py)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -62,17 +63,15 @@ def uv_float64(h: abi.HittableDesc, o: np.ndarray, d: np.ndarray) -> tuple:
     return (o[ia] + t * d[ia] - a0) / (a1 - a0), (o[ib] + t * d[ib] - b0) / (b1 - b0)
 
 
-def query_reference(scene, inputs: abi.InputStruct, width: int, height: int) -> dict:
-    """The rays (n, 2, 4) float32 of the frame's centre rays and rt_query_rays' outputs for them (n = width * height)."""
-    o, d = camera_rays(inputs, width, height, 0.5, 0.5)
-    o, d = o.reshape(-1, 3), d.reshape(-1, 3)
+def records_reference(scene, o: np.ndarray, d: np.ndarray, shifts) -> dict:
+    """rt_query_rays' outputs for the rays (o, d), each (n, 3) float32, by brute force over the description, and the rays
+    themselves as (n, 2, 4) float32.  `shifts`: (o2, d2) pairs of nearby rays; a ray is decidable when every one of them
+    hits the primitive the ray itself hits."""
     n = o.shape[0]
     ids, recs = closest_hits(scene, o, d, records=True)
     decidable = np.ones(n, dtype=bool)
-    e = 1.0 / 64.0
-    for sx, sy in ((e, 0.0), (-e, 0.0), (0.0, e), (0.0, -e)):
-        o2, d2 = camera_rays(inputs, width, height, 0.5 + sx, 0.5 + sy)
-        decidable &= closest_hits(scene, o2.reshape(-1, 3), d2.reshape(-1, 3))[0] == ids
+    for o2, d2 in shifts:
+        decidable &= closest_hits(scene, o2, d2)[0] == ids
     rays = np.zeros((n, 2, 4), dtype=F)
     rays[:, 0, :3], rays[:, 1, :3] = o, d
     nd = np.zeros((n, 4), dtype=F)
@@ -99,6 +98,17 @@ def query_reference(scene, inputs: abi.InputStruct, width: int, height: int) -> 
     for a in out.values():
         a.setflags(write=False)
     return out
+
+
+def query_reference(scene, inputs: abi.InputStruct, width: int, height: int) -> dict:
+    """The rays (n, 2, 4) float32 of the frame's centre rays and rt_query_rays' outputs for them (n = width * height)."""
+    o, d = camera_rays(inputs, width, height, 0.5, 0.5)
+    e = 1.0 / 64.0
+    shifts = []
+    for sx, sy in ((e, 0.0), (-e, 0.0), (0.0, e), (0.0, -e)):
+        o2, d2 = camera_rays(inputs, width, height, 0.5 + sx, 0.5 + sy)
+        shifts.append((o2.reshape(-1, 3), d2.reshape(-1, 3)))
+    return records_reference(scene, o.reshape(-1, 3), d.reshape(-1, 3), shifts)
 
 
 @functools.lru_cache(maxsize=None)

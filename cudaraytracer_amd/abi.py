@@ -23,7 +23,9 @@ RT_FLAG_RNG_PHILOX = 1 << 5
 RT_FLAG_STATE_SOA = 1 << 6
 RT_FLAG_ACCUMULATE_RESET = 1 << 7
 RT_CAMERA_JITTER_PHILOX = 1 << 0
-RT_RADIANCE_DIRECT_LIGHT = 1 << 8  # rt_radiance_args.flags: next-event estimation on the scene's light rectangles
+# rt_radiance_args.flags, rt_adaptive_samples_args.flags, rt_temporal_gradient_args.flags: next-event estimation on the
+# scene's light rectangles
+RT_RADIANCE_DIRECT_LIGHT = 1 << 8
 RT_DENOISE_DEMODULATE = 1 << 0
 RT_DENOISE_COLOR_IS_SUM = 1 << 1
 RT_TEMPORAL_COLOR_IS_SUM = 1 << 0

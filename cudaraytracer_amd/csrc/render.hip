@@ -4721,6 +4721,287 @@ __global__ __launch_bounds__(64, 4) void temporal_gradient_kernel(const Gradient
 }
 
 // ---------------------------------------------------------------------------------------------------
+// RT_RADIANCE_DIRECT_LIGHT in the two fused frame passes (rt_adaptive_samples, rt_temporal_gradient):
+// DirectPath is radiance_direct_kernel's shadow state, two-state traversal and vertex step as one piece, and
+// adaptive_direct_kernel / gradient_direct_kernel are the flagless kernels around it instead of path_vertex and the
+// closest-hit traversal.  A path is the one radiance_direct_kernel runs for the pixel's camera ray of sample s with
+// stream id = the pixel, sample_base = s and one sample: the same vertices, the connection draws of vertex j from words
+// 0..2 of block (s << 16) + 65535 - j, the same light rule, the float sum of the direct terms in vertex order plus the
+// terminal term.  radiance_direct_kernel itself stays as it is written (its pins are exact).
+// ---------------------------------------------------------------------------------------------------
+template <bool COUNT_TESTS, bool WIDE>
+struct DirectPath {
+    f3 acc;          // the path's direct terms so far
+    f3 pend;         // shadow state: the term the shadow ray decides
+    f3 bd;           // shadow state: the bounce ray's direction
+    bool shadow;     // the lane traces (or has traced) a shadow ray
+    bool prev_lamb;  // the path's previous vertex was a Lambertian scatter
+
+    __device__ __forceinline__ void init() {
+        acc = pend = bd = mk(0.0f, 0.0f, 0.0f);
+        shadow = prev_lamb = false;
+    }
+    // a path starts (no shadow ray is under way: a path ends at a closest-hit vertex)
+    __device__ __forceinline__ void begin() {
+        acc = mk(0.0f, 0.0f, 0.0f);
+        prev_lamb = false;
+    }
+    // closest-hit lanes, then shadow lanes
+    // (each call sees the tracing lanes of its state only: it leaves once a quarter of them have finished)
+    __device__ __forceinline__ void trav(const KParams* P, RayWave<WIDE>& w, const uint32_t thr) {
+        if (!shadow) {
+            const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false>(w.nrsrc, P->nodes48, P->refs, P->prims, w.stk, ts, w.ro, w.rd, w.c,
+                                                                w.cnt, 64u, P->leaf_break);
+        }
+        if (shadow && w.c.mode == MODE_TRAV) {
+            const uint32_t ts = min(thr, ((uint32_t)__popcll(__ballot(1)) * 3u) >> 2);
+            v3_traverse<COUNT_TESTS, NODES_48, 0u, WIDE, false, true>(w.nrsrc, P->nodes48, P->refs, P->prims, w.stk, ts, w.ro, w.rd,
+                                                                     w.c, w.cnt, 64u, P->leaf_break, 1e-4f);
+        }
+    }
+    // One MODE_SHADE turn of the lane: the shadow ray's answer and the vertex's bounce ray, or path_vertex's step around
+    // the shadow state — shade() with its VERTEX record, the sampled light's rule between the shading and the depth
+    // rule, and the connection before the bounce ray starts.  DPC: the kernel's params in the constant address space
+    // (lights, light_flags, num_lights: loaded where they are used); window(): (s << 16) of the path's sample.
+    // True: the path ended with `total`; false: the lane's next ray is under way (MODE_TRAV).
+    template <class DPC, class Window>
+    __device__ __forceinline__ bool vertex(RayWave<WIDE>& w, f3& att, RngPhilox& rng, const bool rtl, uint32_t& depth,
+                                           const Window& window, f3& total) {
+        Cursor& c = w.c;
+        KParamsC* const q = kparams_reload();
+        DPC* const dq = (DPC*)q;
+        if (shadow) {
+            if (c.hit < 0) acc = add(acc, pend);
+            shadow = false;
+            w.rd = bd;
+            v3_start_trace<WIDE>(q->num_nodes, c, w.nrays);
+            return false;
+        }
+        if (COUNT_TESTS) w.cnt.wshade += wave_leader();
+        f3 contrib;
+        ShadeVertex vx;
+        const int res = shade<true, false, false, true>(q, q->prims, q->mats, q->imgs, c.hit, c.tag, c.t_best, w.ro, w.rd, att, rng,
+                                                        rtl, contrib, nullptr, &vx);
+        bool ended = res == SHADE_ENDED;
+        // a sampled light after a Lambertian scatter: counted at that vertex
+        if (vx.mtype == RT_DIFFUSELIGHT && prev_lamb && dq->light_flags[c.hit] != 0u) contrib = mk(0.0f, 0.0f, 0.0f);
+        if (!ended && ++depth >= q->max_depth) {  // exceeded recursion (Kernel.cu:79)
+            ended = true;
+            contrib = mk(0.0f, 0.0f, 0.0f);
+        }
+        if (ended) {
+            total = add(acc, contrib);
+            return true;
+        }
+        prev_lamb = vx.mtype == RT_LAMBERTIAN;
+        if (prev_lamb) {  // (vertex j = depth - 1, and j + 1 < max_depth; att is T · a already)
+            philox_block(rng, window() + 65536u - depth);
+            f3 v, D;
+            shadow = light_connection(q, dq->lights, dq->num_lights, philox_to_uniform(rng.r0), philox_to_uniform(rng.r1),
+                                      philox_to_uniform(rng.r2), w.ro, vx.normal, v, D);
+            if (shadow) {
+                pend = mulv(att, D);
+                bd = w.rd;
+                w.rd = v;
+            }
+        }
+        v3_start_trace<WIDE>(q->num_nodes, c, w.nrays);
+        if (shadow) c.t_best = 0.9999f;  // the range's upper end: read by the traversal, never written
+        return false;
+    }
+};
+
+// adaptive_samples_kernel with the light table: its params first, so that a KParams stays at offset 0
+struct AdaptiveDirectParams {
+    AdaptiveParams A;
+    const float4* lights;         // HostScene::light_table: two float4 per sampled light, in list order
+    const uint32_t* light_flags;  // ... and its word per primitive: 1 = a sampled light
+    uint32_t num_lights;          // N_L >= 1
+};
+static_assert(offsetof(AdaptiveDirectParams, A) == 0, "philox_block and kparams_reload read the kernel arguments as a KParams");
+typedef __attribute__((address_space(4))) const AdaptiveDirectParams AdaptiveDirectParamsC;  // (as KParamsC)
+
+// (The counting builds carry both traversals' diagnostic counts: they ask for two waves per SIMD, not four.)
+template <bool COUNT_TESTS, bool WIDE>
+__global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void adaptive_direct_kernel(const AdaptiveDirectParams DQ) {
+    const AdaptiveParams& Q = DQ.A;
+    const KParams* P = &Q.K;
+    const uint32_t entries = Q.count ? min(Q.count[0], Q.capacity) : Q.capacity;  // (wave-uniform)
+    const uint32_t base = blockIdx.x * Q.per_wave;  // (the grid covers capacity: base < capacity)
+    if (base >= entries) return;
+    RayWave<WIDE> w;
+    w.begin(P);
+    Cursor& c = w.c;
+    DirectPath<COUNT_TESTS, WIDE> dp;
+    dp.init();
+    uint32_t npaths = 0u;
+    f3 att = mk(0.0f, 0.0f, 0.0f);
+    SampleSums sums{0u, 0u, 0u};  // the entry's (the accumulation plane's)
+    float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // the pixel's history and moments while the lane owns it
+    float2 mo = make_float2(0.0f, 0.0f);
+    uint32_t pixel = 0u, paths = 0u, sample = 0u, depth = 0u;
+    RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
+    const bool rtl = P->rius_rtl != 0;
+    // (the call's own arguments are loaded where they are used, as in radiance_direct_kernel; the first call stands
+    // above every branch, so that the kernel-argument pointer has one definition)
+    const auto args = []() { return (AdaptiveDirectParamsC*)kparams_reload(); };
+    (void)args();
+    // the pixel's path of sample sample_base + `sample` starts: its own camera ray, then block 1 of the sample's window
+    const auto begin_path = [&]() {
+        AdaptiveDirectParamsC* const A = args();
+        KParamsC* const q = (KParamsC*)A;
+        const uint32_t g = pixel / q->width, x = pixel - g * q->width;
+        camera_ray(q, lane_camera(q, x, g), rng, w.ro, w.rd, A->A.sample_base + sample);
+        att = mk(1.0f, 1.0f, 1.0f);
+        depth = 0u;
+        dp.begin();
+        npaths++;
+        v3_start_trace<WIDE>(q->num_nodes, c, w.nrays);
+    };
+    // a path ended with this sample: the entry's sum, and one more frame's blend of its 2^-12 units
+    const auto merge = [&](const f3 contrib) {
+        const SampleSums one = SampleSums::of(contrib);
+        sums.add(one);
+        AdaptiveDirectParamsC* const A = args();
+        if (A->A.history) {
+            const f3 cs = one.sum();
+            const float N = fminf(h.w + 1.0f, A->A.max_history);
+            const float alpha = 1.0f / N;
+            h = make_float4(h.x + alpha * (cs.x - h.x), h.y + alpha * (cs.y - h.y), h.z + alpha * (cs.z - h.z), N);
+            const float l = (0.2126f * cs.x + 0.7152f * cs.y) + 0.0722f * cs.z;
+            mo = make_float2(mo.x + alpha * (l - mo.x), mo.y + alpha * (l * l - mo.y));
+        }
+    };
+    const auto store = [&]() {
+        AdaptiveDirectParamsC* const A = args();
+        if (A->A.history) A->A.history[pixel] = h;
+        if (A->A.moments) A->A.moments[pixel] = mo;
+        if (A->A.accum) {
+            const float4 a = A->A.accum[pixel];
+            const f3 s = sums.sum();
+            A->A.accum[pixel] = make_float4(a.x + s.x, a.y + s.y, a.z + s.z, a.w + (float)paths);
+        }
+        c.mode = MODE_NEED;
+    };
+    const auto start = [&](uint32_t i) {
+        AdaptiveDirectParamsC* const A = args();
+        pixel = A->A.pixels[i];
+        paths = min(A->A.samples ? A->A.samples[i] : A->A.spp, A->A.max_samples);
+        if (pixel >= A->A.K.width * A->A.K.height || paths == 0u) {  // not an entry: nothing is read or written
+            c.mode = MODE_NEED;
+            return;
+        }
+        rng.pix = pixel;
+        sums = SampleSums{0u, 0u, 0u};
+        sample = 0u;
+        if (A->A.history) h = A->A.history[pixel];
+        if (A->A.moments) mo = A->A.moments[pixel];
+        if (A->A.K.max_depth != 0u) {
+            begin_path();
+        } else {  // exceeded recursion at once (Kernel.cu:79): every sample is 0, nothing is traced
+            npaths += paths;
+            for (uint32_t j = 0; j < paths; j++) merge(mk(0.0f, 0.0f, 0.0f));
+            c.mode = MODE_ENDED;
+        }
+    };
+    const auto step = [&]() {
+        f3 total;
+        if (c.mode == MODE_SHADE &&
+            dp.template vertex<AdaptiveDirectParamsC>(
+                w, att, rng, rtl, depth, [&]() { return (args()->A.sample_base + sample) << 16; }, total)) {
+            merge(total);
+            if (++sample < paths) begin_path();
+            else c.mode = MODE_ENDED;
+        }
+        if (c.mode == MODE_ENDED) store();
+    };
+    ray_wave_run(P, w, base, min(entries - base, Q.per_wave), start, step, [&](const uint32_t thr) { dp.trav(P, w, thr); });
+    w.template finish<COUNT_TESTS>(*P, npaths);
+}
+
+// temporal_gradient_kernel with the light table: its params first, so that a KParams stays at offset 0
+struct GradientDirectParams {
+    GradientParams G;
+    const float4* lights;         // (as AdaptiveDirectParams')
+    const uint32_t* light_flags;
+    uint32_t num_lights;          // N_L >= 1
+};
+static_assert(offsetof(GradientDirectParams, G) == 0, "philox_block and kparams_reload read the kernel arguments as a KParams");
+typedef __attribute__((address_space(4))) const GradientDirectParams GradientDirectParamsC;  // (as KParamsC)
+
+template <bool COUNT_TESTS, bool WIDE>
+__global__ __launch_bounds__(64, COUNT_TESTS ? 2 : 4) void gradient_direct_kernel(const GradientDirectParams DQ) {
+    const GradientParams& Q = DQ.G;
+    const KParams* P = &Q.K;
+    RayWave<WIDE> w;
+    w.begin(P);
+    Cursor& c = w.c;
+    DirectPath<COUNT_TESTS, WIDE> dp;
+    dp.init();
+    const uint32_t base = blockIdx.x * Q.per_wave;
+    uint32_t npaths = 0u;
+    f3 att = mk(0.0f, 0.0f, 0.0f);
+    SampleSums sums{0u, 0u, 0u};  // the stratum's
+    uint32_t item = 0u, pixel = 0u, sample = 0u, depth = 0u;
+    RngPhilox rng{0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};  // (n and pix are carried; philox_block reads key and frame itself)
+    const bool rtl = P->rius_rtl != 0;
+    // (the call's own arguments: loaded where they are used, the first call above every branch, as in adaptive_direct_kernel)
+    const auto args = []() { return (GradientDirectParamsC*)kparams_reload(); };
+    (void)args();
+    // the pixel's path of sample `sample` starts: its own camera ray, then block 1 of the sample's window
+    const auto begin_path = [&]() {
+        KParamsC* const q = kparams_reload();
+        const uint32_t g = pixel / q->width, x = pixel - g * q->width;
+        camera_ray(q, lane_camera(q, x, g), rng, w.ro, w.rd, sample);
+        att = mk(1.0f, 1.0f, 1.0f);
+        depth = 0u;
+        dp.begin();
+        npaths++;
+        v3_start_trace<WIDE>(q->num_nodes, c, w.nrays);
+    };
+    const auto store = [&]() {
+        GradientDirectParamsC* const A = args();
+        const f3 cn = sums.mean((float)A->G.samples);  // rt_radiance_rays' mean
+        const float4 co = A->G.prev_color[pixel];       // (pixel < W·H: both coordinates are clamped)
+        const float delta = (fabsf(cn.x - co.x) + fabsf(cn.y - co.y)) + fabsf(cn.z - co.z);
+        const float level = ((cn.x > co.x ? cn.x : co.x) + (cn.y > co.y ? cn.y : co.y)) + (cn.z > co.z ? cn.z : co.z);
+        A->G.gradient[item] = make_float2(delta, level);  // (item < n: start() is called for indices below count alone)
+        if (A->G.resample) A->G.resample[item] = make_float4(cn.x, cn.y, cn.z, 1.0f);
+        if (A->G.pixel) A->G.pixel[item] = pixel;
+        c.mode = MODE_NEED;
+    };
+    const auto start = [&](uint32_t i) {
+        GradientDirectParamsC* const A = args();
+        item = i;
+        const uint32_t sy = i / A->G.sw, sx = i - sy * A->G.sw;
+        pixel = min(sy * A->G.stride + A->G.off_y, A->G.K.height - 1u) * A->G.K.width +
+                min(sx * A->G.stride + A->G.off_x, A->G.K.width - 1u);
+        rng.pix = pixel;
+        sums = SampleSums{0u, 0u, 0u};
+        sample = 0u;
+        if (A->G.K.max_depth != 0u) {
+            begin_path();
+        } else {  // exceeded recursion at once (Kernel.cu:79): every sample is 0, nothing is traced
+            npaths += A->G.samples;
+            c.mode = MODE_ENDED;
+        }
+    };
+    const auto step = [&]() {
+        f3 total;
+        if (c.mode == MODE_SHADE &&
+            dp.template vertex<GradientDirectParamsC>(w, att, rng, rtl, depth, [&]() { return sample << 16; }, total)) {
+            sums.add(total);
+            if (++sample < args()->G.samples) begin_path();
+            else c.mode = MODE_ENDED;
+        }
+        if (c.mode == MODE_ENDED) store();
+    };
+    ray_wave_run(P, w, base, wave_items(Q.n, base, Q.per_wave), start, step, [&](const uint32_t thr) { dp.trav(P, w, thr); });
+    w.template finish<COUNT_TESTS>(*P, npaths);
+}
+
+// ---------------------------------------------------------------------------------------------------
 // The camera rays of the render kernels as a ray batch (rt_camera_rays): one lane per ray, camera_ray / camera_ray_at
 // and lane_camera themselves.  rays[2i] = (origin, kTmin), rays[2i + 1] = (direction, FLT_MAX): color()'s range.  The
 // params begin with a KParams (camera_ray's Philox draw reads key and frame through the kernel-argument pointer).
@@ -5905,7 +6186,10 @@ int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a
         return (int)RT_ERR_INVALID_ARGUMENT;
     };
     if (!a) return bad("NULL args");
-    if ((a->flags & ~(uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT) != 0) return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT");
+    if ((a->flags & ~((uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT | RT_RADIANCE_DIRECT_LIGHT)) != 0)
+        return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT and RT_RADIANCE_DIRECT_LIGHT");
+    const bool direct = (a->flags & RT_RADIANCE_DIRECT_LIGHT) != 0;
+    if (direct && a->max_depth > 4096u) return bad("max_depth above 4096 with RT_RADIANCE_DIRECT_LIGHT");
     if (a->reserved[0] != 0 || a->reserved[1] != 0) return bad("reserved must be 0");
     if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
     if (a->count_tests > 1u) return bad("count_tests must be 0 or 1");
@@ -5935,8 +6219,9 @@ int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a
     const DeviceScene& S = scene->dev;
     size_t lds;
     if (const int rc = stack_lds("rt_adaptive_samples", S, &lds)) return rc;
-    dev::AdaptiveParams Q;
-    std::memset(&Q, 0, sizeof(Q));
+    dev::AdaptiveDirectParams DQ;
+    std::memset(&DQ, 0, sizeof(DQ));
+    dev::AdaptiveParams& Q = DQ.A;
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
     fill_whole_frame(P, a->width, a->height);  // (global indices, as rt_camera_rays' sparse form)
@@ -5956,6 +6241,13 @@ int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a
     Q.sample_base = a->sample_base;
     Q.max_history = (float)a->max_history;
     const uint32_t grid = wave_grid(a->rays_per_lane, a->capacity, &Q.per_wave);
+    if (direct && S.num_lights != 0u) {  // (without a sampled light the flagged call is the flagless one)
+        DQ.lights = (const float4*)S.light_table;
+        DQ.light_flags = (const uint32_t*)S.light_table + (size_t)S.num_rects * 8u;
+        DQ.num_lights = S.num_lights;
+        return launch_rays("rt_adaptive_samples", RT_RAY_KERNEL(adaptive_direct_kernel, a->count_tests, S.wide_refs), grid, lds,
+                           stream, DQ);
+    }
     return launch_rays("rt_adaptive_samples", RT_RAY_KERNEL(adaptive_samples_kernel, a->count_tests, S.wide_refs), grid, lds,
                        stream, Q);
 }
@@ -5967,7 +6259,10 @@ int rt_temporal_gradient(const rt_scene* scene, const rt_temporal_gradient_args*
         return (int)RT_ERR_INVALID_ARGUMENT;
     };
     if (!a) return bad("NULL args");
-    if ((a->flags & ~(uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT) != 0) return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT");
+    if ((a->flags & ~((uint32_t)RT_FLAG_RIUS_LEFT_TO_RIGHT | RT_RADIANCE_DIRECT_LIGHT)) != 0)
+        return bad("flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT and RT_RADIANCE_DIRECT_LIGHT");
+    const bool direct = (a->flags & RT_RADIANCE_DIRECT_LIGHT) != 0;
+    if (direct && a->max_depth > 4096u) return bad("max_depth above 4096 with RT_RADIANCE_DIRECT_LIGHT");
     if (a->reserved[0] != 0 || a->reserved[1] != 0 || a->reserved[2] != 0) return bad("reserved must be 0");
     if (a->rays_per_lane > 16u) return bad("rays_per_lane above 16");
     if (a->count_tests > 1u) return bad("count_tests must be 0 or 1");
@@ -5996,8 +6291,9 @@ int rt_temporal_gradient(const rt_scene* scene, const rt_temporal_gradient_args*
     const DeviceScene& S = scene->dev;
     size_t lds;
     if (const int rc = stack_lds("rt_temporal_gradient", S, &lds)) return rc;
-    dev::GradientParams Q;
-    std::memset(&Q, 0, sizeof(Q));
+    dev::GradientDirectParams DQ;
+    std::memset(&DQ, 0, sizeof(DQ));
+    dev::GradientParams& Q = DQ.G;
     dev::KParams& P = Q.K;
     fill_scene_tables(P, S);
     fill_whole_frame(P, a->width, a->height);  // (global indices, as rt_adaptive_samples)
@@ -6016,6 +6312,13 @@ int rt_temporal_gradient(const rt_scene* scene, const rt_temporal_gradient_args*
     Q.off_y = a->offset_y;
     Q.samples = a->samples_per_pixel;
     const uint32_t grid = wave_grid(a->rays_per_lane, Q.n, &Q.per_wave);
+    if (direct && S.num_lights != 0u) {  // (without a sampled light the flagged call is the flagless one)
+        DQ.lights = (const float4*)S.light_table;
+        DQ.light_flags = (const uint32_t*)S.light_table + (size_t)S.num_rects * 8u;
+        DQ.num_lights = S.num_lights;
+        return launch_rays("rt_temporal_gradient", RT_RAY_KERNEL(gradient_direct_kernel, a->count_tests, S.wide_refs), grid, lds,
+                           stream, DQ);
+    }
     return launch_rays("rt_temporal_gradient", RT_RAY_KERNEL(temporal_gradient_kernel, a->count_tests, S.wide_refs), grid, lds,
                        stream, Q);
 }

@@ -158,7 +158,8 @@ class DeviceScene:
     def adaptive_samples(self, pixels, inputs: abi.InputStruct, width: int, height: int, depth: int = 8, samples=None,
                          count=None, history=None, moments=None, accum=None, samples_per_pixel: int = 1,
                          max_samples: int = 16, sample_base: int = 1, max_history: int = 32, seed: int = 1984,
-                         frame: int = 0, rays_per_lane: int = 0, left_to_right: bool = False, counters=None) -> None:
+                         frame: int = 0, rays_per_lane: int = 0, left_to_right: bool = False, counters=None,
+                         direct_light: bool = False) -> None:
         """The extra samples of a pixel list, traced and merged in place (rt_adaptive_samples), asynchronous on torch's
         current stream.  pixels: a 32-bit integer (capacity,) device tensor of global pixel indices y * width + x, each
         at most once; samples: the same shape, paths per entry (else samples_per_pixel each, at most max_samples);
@@ -166,7 +167,9 @@ class DeviceScene:
         not read it), else every element of `pixels` is one.  Path j of an entry is sample sample_base + j of that
         pixel's Philox stream (seed, pixel, frame).  Targets, float32 device tensors of the whole frame: history
         (H, W, 4) with or without moments (H, W, 2), blended as further 1-spp frames of rt_temporal_moments would be;
-        accum (H, W, 4), added to as RT_FLAG_ACCUMULATE does."""
+        accum (H, W, 4), added to as RT_FLAG_ACCUMULATE does.  direct_light=True (RT_RADIANCE_DIRECT_LIGHT): every
+        path is the one radiance(..., direct_light=True) runs for that sample's camera ray with the pixel as its stream
+        id."""
         if pixels.dtype not in (torch.int32, torch.uint32) or pixels.dim() != 1 or not pixels.is_cuda or not pixels.is_contiguous():
             raise ValueError("pixels must be a contiguous 32-bit integer (capacity,) tensor on the device")
         if samples is not None and (samples.dtype not in (torch.int32, torch.uint32) or samples.shape != pixels.shape
@@ -188,7 +191,7 @@ class DeviceScene:
         a.capacity, a.width, a.height = pixels.shape[0], width, height
         a.samples_per_pixel, a.max_samples, a.sample_base = samples_per_pixel, max_samples, sample_base
         a.max_depth, a.max_history, a.rays_per_lane = depth, max_history, rays_per_lane
-        a.flags = abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0
+        a.flags = (abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0) | (abi.RT_RADIANCE_DIRECT_LIGHT if direct_light else 0)
         a.rng_seed, a.rng_frame = seed, frame
         a.inputs = inputs
         stream = torch.cuda.current_stream(pixels.device).cuda_stream
@@ -197,13 +200,15 @@ class DeviceScene:
     def temporal_gradient(self, prev_color, inputs: abi.InputStruct, width: int, height: int, depth: int = 8,
                           stride: int = 3, offset=(0, 0), samples_per_pixel: int = 1, seed: int = 1984, frame: int = 0,
                           gradient=None, resample=None, pixel=None, rays_per_lane: int = 0,
-                          left_to_right: bool = False, counters=None):
+                          left_to_right: bool = False, counters=None, direct_light: bool = False):
         """A past Philox frame's samples traced again in this scene and compared with what that frame stored
         (rt_temporal_gradient), asynchronous on torch's current stream.  prev_color: that frame's radiance plane, a
         float32 device tensor of H x W x 4; inputs, seed, frame, samples_per_pixel, depth and left_to_right are that
         frame's.  One pixel per stride x stride stratum, at `offset` = (offset_x, offset_y) inside it.  Outputs, device
         tensors over the ceil(H / stride) x ceil(W / stride) strata: gradient (.., 2) float32 (allocated when None),
-        resample (.., 4) float32 and pixel (..) 32-bit integers, both optional.  Returns gradient."""
+        resample (.., 4) float32 and pixel (..) 32-bit integers, both optional.  direct_light=True
+        (RT_RADIANCE_DIRECT_LIGHT): that frame was drawn with light sampling, and is traced again with it.  Returns
+        gradient."""
         if (prev_color.dtype != torch.float32 or prev_color.numel() != width * height * 4 or not prev_color.is_cuda
                 or not prev_color.is_contiguous()):
             raise ValueError(f"prev_color must be a contiguous float32 tensor of {height} x {width} x 4 on the device")
@@ -224,7 +229,7 @@ class DeviceScene:
                 setattr(a, name, t.data_ptr())
         a.width, a.height, a.stride, a.offset_x, a.offset_y = width, height, stride, int(offset[0]), int(offset[1])
         a.samples_per_pixel, a.max_depth, a.rays_per_lane = samples_per_pixel, depth, rays_per_lane
-        a.flags = abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0
+        a.flags = (abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0) | (abi.RT_RADIANCE_DIRECT_LIGHT if direct_light else 0)
         a.rng_seed, a.rng_frame = seed, frame
         a.tiling = abi.Tiling(max(height, 1), 1, 0, height)
         a.inputs = inputs
@@ -375,6 +380,8 @@ class Renderer:
         self.gradient = None
         self._radiance_frame = None
         self._gradient_calls = 0
+        # render_direct(): every pixel in ascending order, the frame's sums and the divisor, allocated on first use
+        self._all_pixels = self._direct_accum = self._direct_spp = None
 
     def tiling(self) -> abi.Tiling:
         return abi.Tiling(self.band_rows, self.num_ranks, self.rank, self.local_rows)
@@ -433,6 +440,44 @@ class Renderer:
             self._radiance_frame = ((abi.InputStruct.from_buffer_copy(inputs), self.seed, frame, spp, flags)
                                     if self.rng == "philox" else None)
         return self.pos
+
+    def render_direct(self, scene: DeviceScene, inputs: abi.InputStruct, spp: int = 1, depth: int = 8,
+                      direct_light: bool = True, left_to_right: bool = False) -> torch.Tensor:
+        """One whole Philox frame through the fused pass (rt_adaptive_samples over every pixel, samples 0 .. spp - 1,
+        spp in 1..16, into a zeroed sum plane), with light sampling (RT_RADIANCE_DIRECT_LIGHT) unless direct_light is
+        False; asynchronous on torch's current stream.  Stores `radiance` = (the samples' sum / spp, 1) per pixel — the
+        plane temporal() and temporal_gradient() read — and records the frame, its flag bits included, so that
+        temporal_gradient() traces it again with the same estimator and adaptive() continues it.  Draws the next frame
+        counter value, as render() does.  Whole frames of a Philox renderer only; nothing is synchronised.  Returns
+        `radiance`."""
+        if self.rng != "philox":
+            raise RTError("render_direct: the renderer's rng must be 'philox'")
+        if self.num_ranks != 1:
+            raise RTError("render_direct: whole frames only (num_ranks = 1)")
+        if not 1 <= spp <= 16:
+            raise ValueError("spp must be 1..16")
+        n = self.width * self.height
+        if self._all_pixels is None:
+            self._all_pixels = torch.arange(n, dtype=torch.int32, device=self.device)
+            self._direct_accum = torch.zeros((n, 4), dtype=torch.float32, device=self.device)
+            self._direct_spp = torch.zeros(1, dtype=torch.float32, device=self.device)
+        if self.radiance is None:
+            self.radiance = torch.zeros(n * 4, dtype=torch.float32, device=self.device)
+        frame = self.frame
+        self.frame += 1
+        self._direct_accum.zero_()
+        scene.adaptive_samples(self._all_pixels, inputs, self.width, self.height, depth, accum=self._direct_accum,
+                               samples_per_pixel=spp, max_samples=16, sample_base=0, seed=self.seed, frame=frame,
+                               left_to_right=left_to_right, direct_light=direct_light)
+        out = self.radiance.view(n, 4)
+        self._direct_spp.fill_(float(spp))
+        # (a tensor divisor: a Python scalar would be turned into a multiplication by its reciprocal)
+        torch.div(self._direct_accum[:, :3], self._direct_spp, out=out[:, :3])
+        out[:, 3] = 1.0
+        flags = (abi.RT_FLAG_RNG_PHILOX | (abi.RT_FLAG_RIUS_LEFT_TO_RIGHT if left_to_right else 0)
+                 | (abi.RT_RADIANCE_DIRECT_LIGHT if direct_light else 0))
+        self._radiance_frame = (abi.InputStruct.from_buffer_copy(inputs), self.seed, frame, spp, flags)
+        return self.radiance
 
     def reset_accumulation(self) -> None:
         """Restart the progressive sums (camera move, scene edit): the next accumulating frame passes
@@ -620,27 +665,34 @@ class Renderer:
 
     def adaptive(self, scene: DeviceScene, inputs: abi.InputStruct, depth: int, tau: float = 0.1, min_history: int = 4,
                  max_samples: int = 4, capacity: int | None = None, frame: int | None = None, seed: int | None = None,
-                 sample_base: int = 1, max_history: int = 32, lum_floor: float = 0.01) -> torch.Tensor:
+                 sample_base: int = 1, max_history: int = 32, lum_floor: float = 0.01,
+                 direct_light: bool | None = None) -> torch.Tensor:
         """Adaptive sampling on the device: adaptive_select(), then DeviceScene.adaptive_samples() on the list, merged
         into the current `history` and `moments` planes in place.  Call after temporal(moments=True) and before
         denoise_variance(); whole frames only.  The extra samples of a pixel are samples sample_base .. of the Philox
         stream (seed, pixel, frame): with the defaults — the renderer's seed, the frame render() drew last, sample 1 on
         — they continue a 1-spp Philox frame.  max_history is temporal()'s.  Nothing is synchronised: returns the
-        device `count` tensor (listed pixels, extra samples)."""
+        device `count` tensor (listed pixels, extra samples).  direct_light: trace the extra samples with light sampling
+        (RT_RADIANCE_DIRECT_LIGHT); None takes what the recorded frame — the last render(radiance=True) or
+        render_direct() — was drawn with."""
+        if direct_light is None:
+            direct_light = bool(self._radiance_frame is not None and self._radiance_frame[4] & abi.RT_RADIANCE_DIRECT_LIGHT)
         pixels, samples, count = self.adaptive_select(tau, min_history, max_samples, capacity, lum_floor)
         if pixels.shape[0]:
             scene.adaptive_samples(pixels, inputs, self.width, self.height, depth, samples=samples, count=count,
                                    history=self.history, moments=self.moments, max_samples=max_samples,
                                    sample_base=sample_base, max_history=max_history,
                                    seed=self.seed if seed is None else seed,
-                                   frame=max(self.frame - 1, 0) if frame is None else frame)
+                                   frame=max(self.frame - 1, 0) if frame is None else frame,
+                                   direct_light=direct_light)
         return count
 
     def temporal_gradient(self, scene: DeviceScene, depth: int, stride: int = 3, radius: int = 1, power: int = 4,
                           gain: float = 1.0, lum_floor: float = 0.01) -> torch.Tensor:
         """Cut stale history after a scene edit (rt_temporal_gradient, then rt_history_adapt): call after the edit and
         before the next render(), on frames with an edit only; whole frames only.  `scene` is the edited scene.  The
-        last render(..., radiance=True) — its `radiance` plane, inputs, seed, frame number, spp and fill order; it must
+        last render(..., radiance=True) or render_direct() — its `radiance` plane, inputs, seed, frame number, spp, fill
+        order and light sampling; it must
         have been a Philox frame, and `depth` must be the depth it was drawn with — is traced again in `scene` at one
         pixel per stride x stride stratum, and the current `history` plane's lengths are scaled in place by
         (1 - lambda)^power, lambda from the strata within `radius` of the pixel's.  The pixel's place in its stratum
@@ -664,7 +716,7 @@ class Renderer:
         a.prev_color, a.gradient = self.radiance.data_ptr(), self.gradient.data_ptr()
         a.width, a.height, a.stride, a.offset_x, a.offset_y = self.width, self.height, stride, turn % stride, turn // stride
         a.samples_per_pixel, a.max_depth = spp, depth
-        a.flags = flags & abi.RT_FLAG_RIUS_LEFT_TO_RIGHT
+        a.flags = flags & (abi.RT_FLAG_RIUS_LEFT_TO_RIGHT | abi.RT_RADIANCE_DIRECT_LIGHT)
         a.rng_seed, a.rng_frame = seed, frame
         a.tiling = self.tiling()
         a.inputs = inputs

@@ -190,7 +190,8 @@ const char* rt_version(void);
  * rt_set_tile_occlusion, rt_tile_entries_device, rt_occluded_rays, rt_camera_rays, rt_radiance_rays,
  * rt_set_bounce_classes, rt_bounce_class_entries_host, rt_adaptive_select, rt_adaptive_select_scratch_bytes,
  * rt_adaptive_samples, rt_temporal_gradient, rt_history_adapt, RT_RADIANCE_DIRECT_LIGHT, rt_scene_lights_host (a caller
- * asks the library for them by name). */
+ * asks the library for them by name), RT_RADIANCE_DIRECT_LIGHT in rt_adaptive_samples_args.flags and
+ * rt_temporal_gradient_args.flags (a library without it answers RT_ERR_INVALID_ARGUMENT, "flags"). */
 #define RT_ABI_VERSION 14
 int rt_abi_version(void);
 
@@ -876,12 +877,24 @@ int rt_adaptive_select(const rt_adaptive_select_args* args, rt_stream stream);
  *   incoming history.w is used as it is, 0 included.
  *   accum (float4, in place): rgb += (the saturating sum of the k_i samples' 2^-12 units) / 4096, one float add per
  *   channel, w += k_i: what RT_FLAG_ACCUMULATE adds for k_i samples.
- * counters[0]: color() iterations, counters[3]: paths; count_tests as rt_radiance_rays.  flags: 0 or
- * RT_FLAG_RIUS_LEFT_TO_RIGHT.  The result does not depend on rays_per_lane, on rt_set_tuning or on the call.
+ * counters[0]: color() iterations, counters[3]: paths; count_tests as rt_radiance_rays.  flags: 0,
+ * RT_FLAG_RIUS_LEFT_TO_RIGHT, RT_RADIANCE_DIRECT_LIGHT or both.  The result does not depend on rays_per_lane, on
+ * rt_set_tuning or on the call.
+ * RT_RADIANCE_DIRECT_LIGHT (rt_radiance_rays' flag, defined there): path j of entry i is the path rt_radiance_rays with
+ * the flag runs for the camera ray of that pixel's sample s = sample_base + j (rt_camera_rays with
+ * RT_CAMERA_JITTER_PHILOX, sample = s) with stream id = the pixel index, sample_base = s and samples_per_ray = 1: the
+ * same vertices, the connection draws of vertex v from words 0-2 of block (s << 16) + 65535 - v, the same light choice,
+ * point and shadow range (1e-4, 0.9999), the same emission rule for a sampled light after a Lambertian scatter, and the
+ * sample as the float sum of its direct terms in vertex order plus the terminal term, quantised once.  c_s is that
+ * quantised sample; it is merged exactly as a flagless one (history / moments blend per path in order, accum as the
+ * saturating unit sum).  counters[0] also counts the shadow rays; counters[3] is unchanged.  max_depth above 4096 with
+ * the flag is RT_ERR_INVALID_ARGUMENT.  A scene without a sampled light (rt_scene_lights_host: 0) runs the flagless
+ * call.  The independence of rays_per_lane, rt_set_tuning and the call holds as without the flag.
  * RT_ERR_INVALID_ARGUMENT, before any device call and before the scene is read: NULL scene, NULL args, no target,
  * moments without history, samples_per_pixel = 0 without samples, max_samples outside 1..16, sample_base + max_samples
  * above RT_PHILOX_MAX_SPP, max_history outside 1..4096, rays_per_lane above 16, count_tests other than 0 or 1 or 1
- * without counters, other flag bits, non-zero reserved words, width·height beyond 31 bits; with capacity > 0: NULL
+ * without counters, other flag bits, max_depth above 4096 with RT_RADIANCE_DIRECT_LIGHT, non-zero reserved words,
+ * width·height beyond 31 bits; with capacity > 0: NULL
  * pixels, a zero width or height, any two of pixels, samples, count, counters, history, moments and accum that overlap.
  * capacity = 0: RT_OK.  A BVH deeper than 64 levels: RT_ERR_UNSUPPORTED. */
 typedef struct rt_adaptive_samples_args {
@@ -901,7 +914,7 @@ typedef struct rt_adaptive_samples_args {
     uint32_t max_history;       /* 1..4096, as rt_temporal_args */
     uint32_t rays_per_lane;     /* entries per lane: 0 = automatic, 1..16 (changes the schedule only) */
     uint32_t count_tests;       /* 0 or 1 */
-    uint32_t flags;             /* 0 or RT_FLAG_RIUS_LEFT_TO_RIGHT */
+    uint32_t flags;             /* RT_FLAG_RIUS_LEFT_TO_RIGHT, RT_RADIANCE_DIRECT_LIGHT or both, or 0 */
     uint32_t rng_frame;
     uint64_t rng_seed;
     rt_input_struct inputs;     /* the frame's camera and sky */
@@ -941,9 +954,22 @@ int rt_adaptive_samples(const rt_scene* scene, const rt_adaptive_samples_args* a
  * global index y·width + x), optional.  counters, count_tests and rays_per_lane as rt_adaptive_samples: they change
  * the schedule only.  One asynchronous launch; every element is written once, by the lane that traced it; no atomics
  * outside the counters.  max_depth = 0: c_new = 0.
+ * flags: 0, RT_FLAG_RIUS_LEFT_TO_RIGHT, RT_RADIANCE_DIRECT_LIGHT or both, as the previous frame's.  With
+ * RT_RADIANCE_DIRECT_LIGHT the previous frame has to have been drawn with the flag (rt_adaptive_samples' fused frame,
+ * or rt_camera_rays + rt_radiance_rays with the flag and stream id = the pixel index): sample j of a stratum is then the
+ * path rt_radiance_rays with the flag runs for the camera ray of that pixel's sample j (RT_CAMERA_JITTER_PHILOX,
+ * sample = j) with stream id = the pixel index, sample_base = j and samples_per_ray = 1 - the same vertices, the
+ * connection draws of vertex v from words 0-2 of block (j << 16) + 65535 - v, the same light choice, point and shadow
+ * range (1e-4, 0.9999), the same emission rule for a sampled light after a Lambertian scatter, the sample as the float
+ * sum of its direct terms in vertex order plus the terminal term, quantised once - and the samples are summed and c_new,
+ * δ and m formed as without it, so an unedited scene gives δ = 0 exactly.  A flagless re-trace of a flagged frame, or
+ * the reverse, differs in almost every stratum.  counters[0] also counts the shadow rays; counters[3] is unchanged.
+ * max_depth above 4096 with the flag is RT_ERR_INVALID_ARGUMENT; a scene without a sampled light runs the flagless
+ * call.  The independence of rays_per_lane, rt_set_tuning and the call holds as without the flag.
  * RT_ERR_INVALID_ARGUMENT, before any device call and before the scene is read: NULL scene, NULL args, NULL prev_color
  * or gradient, stride outside 1..8, an offset not below stride, samples_per_pixel outside 1..16, rays_per_lane above 16,
- * count_tests other than 0 or 1 or 1 without counters, flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT, non-zero reserved
+ * count_tests other than 0 or 1 or 1 without counters, flags other than RT_FLAG_RIUS_LEFT_TO_RIGHT and
+ * RT_RADIANCE_DIRECT_LIGHT, max_depth above 4096 with RT_RADIANCE_DIRECT_LIGHT, non-zero reserved
  * words, tiling.num_ranks > 1 or local_rows neither 0 nor height, width·height beyond 31 bits, any two of prev_color,
  * gradient, resample, pixel and counters that overlap.  width·height = 0: RT_OK.  A BVH deeper than 64 levels:
  * RT_ERR_UNSUPPORTED. */
@@ -961,7 +987,7 @@ typedef struct rt_temporal_gradient_args {
     uint32_t max_depth;         /* the previous frame's */
     uint32_t rays_per_lane;     /* strata per lane: 0 = automatic, 1..16 (changes the schedule only) */
     uint32_t count_tests;       /* 0 or 1 */
-    uint32_t flags;             /* 0 or RT_FLAG_RIUS_LEFT_TO_RIGHT, as the previous frame's */
+    uint32_t flags;             /* RT_FLAG_RIUS_LEFT_TO_RIGHT, RT_RADIANCE_DIRECT_LIGHT or both, or 0: the previous frame's */
     uint32_t rng_frame;         /* the previous frame's */
     uint32_t reserved[3];       /* must be 0 */
     rt_tiling tiling;           /* whole frame only, as rt_temporal */
